@@ -30,7 +30,16 @@ touching any GPU, and exits with its status; under torchrun WORLD_SIZE must equa
       the launcher, the sharding / limb partition + gather and the timing path on a machine without
       a GPU.  Its numbers measure nothing.
 
-Also reported on the same JSON line:
+A plain run sets up, warms up, times the K steps, writes its outputs when --dump-outputs DIR is
+given, and prints the JSON line; nothing else touches the GPU or the host cores.
+  --dump-outputs DIR: after the timed steps, what the last step's pass over input copy 0 wrote (the
+      array a caller of the path receives), as float64 .npy files.  The residues are up to 60 bits
+      wide, so every value x is stored exactly as two arrays, out_lo32.npy = x mod 2^32 and
+      out_hi.npy = x >> 32, of the same shape; a larger batch is cut to a fixed, seeded sample of
+      its work items (items.npy: their indices) so that the files stay under 48 MB.  The inputs are
+      seeded and do not depend on the timing, so two builds can be compared value for value.
+
+With --full, also reported on the same JSON line (each takes GPU or CPU runs of its own):
   roofline     — the kernel family with the largest share of one profiled batch (HIP events around
                  each of its launches, on the stream it runs on), its ALGORITHMIC bytes per launch
                  (each operand read once, each result written once) over its average
@@ -38,7 +47,8 @@ Also reported on the same JSON line:
                  `kernels` the whole profiled breakdown;
   cpu_baseline — the C restatement of the reference algorithm (oracle/c: exact BigInt schoolbook
                  tensor, eval.rs:113-147; dbfv_mul with all d^2 products) on a bounded sample of the
-                 same workload, on the host cores, rank 0 at N=1 only.
+                 same workload, on the host cores, rank 0 at N=1 only;
+  latency      — one call of the path on one unit (batch 1), median over 30 synchronised calls.
 """
 
 from __future__ import annotations
@@ -106,9 +116,15 @@ def parse(argv=None):
     ap.add_argument("--min-time", type=float, default=3.0, help="lower bound of the timed region, seconds")
     ap.add_argument("--reps", type=int, default=0, help="batches per step (0 = from --min-time)")
     ap.add_argument("--dry", action="store_true", help="no HIP calls: CPU/gloo stand-in of the step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline / per-kernel profile, the batch-1 "
+                         "latency block and the CPU baseline (off by default: a plain run does only "
+                         "what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-latency", action="store_true",
-                    help="skip the batch-1 latency block (PMC passes: only full-batch dispatches)")
+                    help="with --full: skip the batch-1 latency block (PMC passes: only full-batch dispatches)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="units timed for the CPU baseline (0 = auto)")
     return ap.parse_args(argv)
 
@@ -325,6 +341,28 @@ def latency_block(one_single, sync, reps=30):
     ts.sort()
     return {"median_us": round(1e6 * ts[len(ts) // 2], 1), "min_us": round(1e6 * ts[0], 1), "calls": reps,
             "batch": 1}
+
+
+DUMP_BYTES = 48_000_000   # upper bound of what --dump-outputs writes
+
+
+def dump_outputs(out, d):
+    """Write the (B, ...) int64 residue tensor `out` to d/out_lo32.npy and d/out_hi.npy (float64, exact:
+    x = hi * 2^32 + lo), cut to a fixed seeded sample of its B work items when it is too large;
+    d/items.npy lists the items written, in order."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    B = out.shape[0]
+    per_item = out[0].numel() * 16   # two float64 per value
+    k = max(1, min(B, DUMP_BYTES // per_item))
+    items = np.arange(B) if k == B else np.sort(np.random.default_rng(0xD0).choice(B, size=k, replace=False))
+    sel = out.index_select(0, torch.as_tensor(items, dtype=torch.int64, device=out.device))
+    np.save(os.path.join(d, "out_lo32.npy"), (sel & 0xFFFFFFFF).to(torch.float64).cpu().numpy())
+    np.save(os.path.join(d, "out_hi.npy"), (sel >> 32).to(torch.float64).cpu().numpy())
+    np.save(os.path.join(d, "items.npy"), items.astype(np.float64))
+    return {"dir": d, "arrays": ["out_lo32", "out_hi", "items"], "items": int(k), "of": int(B),
+            "shape": list(sel.shape), "encoding": "value = out_hi * 2^32 + out_lo32 (float64, exact)"}
 
 
 def main():
@@ -571,6 +609,10 @@ def main():
         for r in range(reps):
             one(r % nbuf)
 
+    if args.dump_outputs:
+        # what is written afterwards then comes from the timed steps, not from the warm-up
+        for o in outs:
+            o.zero_()
     if distributed:
         # the timed region: one deadline plus ten times its expected length
         wd.arm("timed", xdist.deadline_s() + 10.0 * args.steps * reps * per)
@@ -597,12 +639,18 @@ def main():
         # stand-in chain: every step adds y, so the assembled output is x + depth * y on every limb
         dry_check = bool(torch.equal(outs[(reps - 1) % nbuf], x[(reps - 1) % nbuf] + depth * y[(reps - 1) % nbuf]))
 
+    # every step's first pass reads input copy 0 and writes outs[0], whatever `reps` came out as
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(outs[0], args.dump_outputs)
+
+    # ---- everything below the headline figure: only with --full
     roofline, ntt, kernels = None, None, None
-    if not args.dry:
+    if args.full and not args.dry:
         roofline, ntt, kernels = roofline_block(ctx, lambda: one(0), args.config, n, L, S)
 
     latency = None
-    if one_single is not None and not args.dry and world == 1 and not args.no_latency:
+    if args.full and one_single is not None and not args.dry and world == 1 and not args.no_latency:
         latency = latency_block(one_single, sync)
         if args.config in PUBLISHED:
             pub = PUBLISHED[args.config]
@@ -610,7 +658,7 @@ def main():
             latency["reference_source"] = pub["source"] + "; reference Rust CPU, hardware unstated"
 
     cpu = None
-    if (rank == 0 and world == 1 and not args.dry and not args.no_cpu_baseline
+    if (args.full and rank == 0 and world == 1 and not args.dry and not args.no_cpu_baseline
             and args.config != "galois"):
         try:   # informative; never fail the bench on it
             cpu = cpu_baseline(args.config, n, moduli, aux, plain, gbase, dbfv, depth, args.cpu_sample)
@@ -658,6 +706,8 @@ def main():
             "key_broadcast": key_collective,
             "rccl_nranks": rccl_nranks,
             "timed_s": round(elapsed, 3),
+            "full": args.full,
+            "dumped_outputs": dumped,
             "roofline": roofline,
             "ntt": ntt,
             "kernels": kernels,

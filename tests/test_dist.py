@@ -164,6 +164,31 @@ def test_bench_dry_gpus8_cfg4_split_keeps_every_rank_busy():
     assert sum(cnt for cnt, _ in ranks) * 1 == 16 * line["config"]["split_plan"]["limb_groups"]
 
 
+def test_bench_dry_dump_outputs_is_exact_and_repeatable(tmp_path):
+    """--dump-outputs writes float64 halves that rebuild the last step's output exactly (the dry
+    stand-in: ct1 + ct2 of input copy 0), the same values whatever the timing chose for the batches
+    per step; a plain run carries none of the --full blocks."""
+    import numpy as np
+    lines = []
+    for name, min_time, steps in (("a", "0.05", "2"), ("b", "0.3", "3")):
+        rc, line, r = _bench("--gpus", "1", "--dry", "--config", "cfg3", "--batch", "3", "--steps", steps,
+                             "--warmup", "1", "--min-time", min_time, "--dump-outputs", str(tmp_path / name))
+        assert rc == 0, r.stderr[-2000:]
+        assert line["steps"] == int(steps) and line["ms_per_step"] > 0 and line["full"] is False
+        assert all(line[k] is None for k in ("roofline", "ntt", "kernels", "cpu_baseline", "latency"))
+        lines.append(line)
+    got = {}
+    for name in ("a", "b"):
+        lo, hi = np.load(tmp_path / name / "out_lo32.npy"), np.load(tmp_path / name / "out_hi.npy")
+        assert lo.dtype == hi.dtype == np.float64 and lo.shape == hi.shape == (3, 2, 3, 4096)
+        assert np.array_equal(np.load(tmp_path / name / "items.npy"), np.arange(3.0))
+        assert lo.max() < 2.0 ** 32 and hi.max() < 2.0 ** 29 and np.all(lo == np.floor(lo))
+        got[name] = (lo, hi)
+    assert np.array_equal(got["a"][0], got["b"][0]) and np.array_equal(got["a"][1], got["b"][1])
+    # sums of two residues below 2^60: above 2^53 for most, so a single float64 would have rounded them
+    assert got["a"][1].max() >= 2.0 ** 27 and len(np.unique(got["a"][0])) > 70000
+
+
 def test_split_plan_shapes():
     from exacto_amd.dist import split_plan
     # cfg4 batch over 8 ranks: whole items (no exchange between chain steps), 2 items each

@@ -9,7 +9,7 @@ for c in ${@:-cfg3}; do
   for rep in 1 2; do
     for v in cur $VARS; do
       L=""; [ $v != cur ] && L=$R/build/ab/$v.so
-      EXACTO_HIP_LIB=$L timeout -k 10 200 python3 bench.py --config $c --no-cpu-baseline --min-time 1.5 > $O/${v}_${c}_$rep.json 2>> $O/err.log || exit 1
+      EXACTO_HIP_LIB=$L timeout -k 10 200 python3 bench.py --full --config $c --no-cpu-baseline --min-time 1.5 > $O/${v}_${c}_$rep.json 2>> $O/err.log || exit 1
       python3 - $O/${v}_${c}_$rep.json $v $c <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
