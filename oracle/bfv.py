@@ -138,6 +138,8 @@ def poly_mul_exact(a: list[int], b: list[int]) -> list[int]:
         return poly_mul_schoolbook(a, b)
     ma = max((abs(x) for x in a), default=0)
     mb = max((abs(x) for x in b), default=0)
+    if ma == 0 or mb == 0:      # a zero operand: the packing width below would not hold the other one
+        return [0] * n
     bound = 2 * n * ma * mb + 1
     kb = (bound.bit_length() + 8) // 8 + 1
     ap = _pack([x if x > 0 else 0 for x in a], kb)

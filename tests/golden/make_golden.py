@@ -17,6 +17,7 @@
 Run: python tests/golden/make_golden.py   (takes ~1 minute)
      python tests/golden/make_golden.py --dbfv-digests   (~10 minutes on 8 cores)
      python tests/golden/make_golden.py --worst-digests  (~5 minutes: tests/worstcase.py inputs at cfg5)
+     python tests/golden/make_golden.py --boundary-digests  (~3 minutes: tests/fp_boundary.py inputs at n = 8192)
 """
 
 import hashlib
@@ -264,6 +265,34 @@ def worst_digests(threads):
     return out
 
 
+# Inputs at the centring boundary of the float-sum scale paths (tests/fp_boundary.py) at n = 8192, where
+# the C restatement needs minutes: dbfv_mul at cfg5 (psum adding Garner-fallback and float-sum products into
+# one carry) and bfv_mul_and_relin over the four lowest special primes == 1 mod 16384 (d about 2^23.9).
+# Item 0 is the pinned item; the GPU test (tests/test_gpu_fp_boundary.py) pads cfg5 to the bench's batch.
+BOUNDARY = {
+    "boundary_cfg5_dbfv": {"n": 8192, "op": "dbfv_mul"},
+    "boundary_low4_bfv": {"n": 8192, "op": "bfv_mul_and_relin"},
+}
+
+
+def boundary_digests(threads):
+    import time
+    from oracle import cref
+    import fp_boundary as F
+    out = {}
+    for name, spec in BOUNDARY.items():
+        t0 = time.time()
+        prm, x, y, rlk = F.digest_inputs(name)
+        fn = cref.dbfv_mul if spec["op"] == "dbfv_mul" else cref.bfv_mul_and_relin
+        r = fn(prm, x, y, rlk, threads=threads)
+        e = dict(spec, generator="tests/fp_boundary.py digest_inputs(name)")
+        e["sha256_inputs"] = input_digest(x, y, rlk)
+        e["sha256_out"] = sha(r)
+        out[name] = e
+        print(name, e["sha256_out"], f"{time.time() - t0:.1f} s", flush=True)
+    return out
+
+
 # The bench's production shapes (bench.py DEFAULT_BATCH), so that the exact batch the bench times,
 # at the library's default chunking and pipeline lanes, is compared against the C restatement:
 #   cfg3    bfv_mul_and_relin, B = 1024 (two 512-product chunks on two lanes; eval.rs:73-147)
@@ -362,6 +391,13 @@ def main():
         with open(os.path.join(HERE, "digests.json")) as f:
             dg = json.load(f)
         dg.update(bench_digests(threads=os.cpu_count() or 1, names=names))
+        with open(os.path.join(HERE, "digests.json"), "w") as f:
+            json.dump(dg, f, indent=1)
+        return
+    if "--boundary-digests" in sys.argv:
+        with open(os.path.join(HERE, "digests.json")) as f:
+            dg = json.load(f)
+        dg.update(boundary_digests(threads=os.cpu_count() or 1))
         with open(os.path.join(HERE, "digests.json"), "w") as f:
             json.dump(dg, f, indent=1)
         return

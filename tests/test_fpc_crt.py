@@ -6,7 +6,8 @@ and cfg5 (primes == 1 mod 2n just below 2^60, P > 4 p n Q), extremes included.  
 make |r| < P / 4 hold: the scale's |r| <= p n Q / 2 + 1 < P / 8, and psum_fp_max's m (2 p n Q + 4) <= P.
 
 A Python restatement of the device arithmetic (each fp64 operation correctly rounded, as gfx950's
-v_cvt_f64_u32 / v_add_f64 / v_fma_f64 are), not the kernel."""
+v_cvt_f64_u32 / v_add_f64 / v_fma_f64 are), not the kernel.  The kernel's lift runs behind both the float
+sum and the Garner fallback, for L = 2 .. 6, in tests/test_gpu_fp_boundary.py."""
 import math
 import random
 from fractions import Fraction

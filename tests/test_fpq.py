@@ -7,7 +7,9 @@ fast path is taken and sum_i z_i (Q / q_i) - beta Q equals the centred s the Gar
 path's T_a pq Pi_a + sum_k v_k fpc_qpq[k][a] + negs Pi_a mod every p_a.  Random residues, zeros, and s
 driven to within a few units (and within 2^-45 Q) of +-Q/2, where the band must send the lane to Garner.
 
-A Python restatement of the device arithmetic (each fp64 operation correctly rounded), not the kernel."""
+A Python restatement of the device arithmetic (each fp64 operation correctly rounded), not the kernel.
+The kernels themselves run the same boundary (both sides of the band within one wave, psum adding fallback
+and flushed products into one carry) in tests/test_gpu_fp_boundary.py, on inputs from tests/fp_boundary.py."""
 import math
 import random
 from fractions import Fraction

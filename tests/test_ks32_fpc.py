@@ -8,7 +8,9 @@ below 2^32 / 3, wide below 2^31, lazy below 2^30) for the cfg3 / cfg4 / cfg5 par
 pushed to the margin's limit; and four narrow / lazy primes (cfg5's ring at base 2^16).
 
 A Python restatement of the device arithmetic (each fp64 operation correctly rounded, as gfx950's
-v_cvt_f64_u32 / v_mul_f64 / v_fma_f64 are), not the kernel."""
+v_cvt_f64_u32 / v_mul_f64 / v_fma_f64 are), not the kernel.  The kernel reduces mod q = 2^60 - d with d
+about 2^23.9 (the bottom of the special window) in tests/test_gpu_fp_boundary.py; its largest |u| is
+driven by tests/test_gpu_worstcase.py."""
 import math
 import random
 from fractions import Fraction

@@ -65,7 +65,8 @@ def cfg5(out):
     prm5 = dp.bfv_params
     q5, d = prm5.ct_basis.moduli, dp.num_digits
     rng = np.random.default_rng(7002)
-    # three items: the chain batch splits 2 + 1 over the context and its twin (EXACTO_CHAIN_SPLIT)
+    # three items: the chain batch runs 1 + 1 + 1 over the context and two twins, three streams
+    # (EXACTO_CHAIN_SPLIT; chains ask for four parts)
     a = uniform_residues(rng, (3, d, 2), q5, 8192)
     b = uniform_residues(rng, (3, d, 2), q5, 8192)
     rlk5 = uniform_residues(rng, (prm5.gadget_digits, 2), q5, 8192)
