@@ -95,6 +95,23 @@ _SIGS = [
     ("exacto_dbfv_decrypt_poly", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
     ("exacto_dbfv_decrypt_poly_dev", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
     ("exacto_dbfv_mul_chain_dev", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ, _SZ], C.c_int),
+    *[(f"exacto_dbfv_encrypt_{kind}{sfx}", [_P, _SZ, _U64, _U64, _P, _P, C.c_double, _P, _U64, _P, _SZ], C.c_int)
+      for kind in ("sk", "pk", "poly_sk", "poly_pk") for sfx in ("", "_dev")],
+    *[(f"exacto_dbfv_{op}{sfx}", [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P], C.c_int)
+      for op in ("add", "sub") for sfx in ("", "_dev")],
+    ("exacto_dbfv_neg", [_P, _P, _SZ, _SZ, _P, _SZ], C.c_int),
+    ("exacto_dbfv_neg_dev", [_P, _P, _SZ, _SZ, _P, _SZ], C.c_int),
+    ("exacto_dbfv_relinearize", [_P, _P, _SZ, _SZ, _P, _SZ], C.c_int),
+    ("exacto_dbfv_relinearize_dev", [_P, _P, _SZ, _SZ, _P, _SZ], C.c_int),
+    ("exacto_dbfv_apply_automorphism", [_P, _P, _SZ, _SZ, _U64, _P, _SZ, _P, _SZ], C.c_int),
+    ("exacto_dbfv_apply_automorphism_dev", [_P, _P, _SZ, _SZ, _U64, _P, _SZ, _P, _SZ], C.c_int),
+    ("exacto_dbfv_linear_map", [_P, _SZ, _SZ, _SZ, _P, _P, _P, _SZ], C.c_int),
+    ("exacto_dbfv_linear_map_dev", [_P, _SZ, _SZ, _SZ, _P, _P, _P, _SZ], C.c_int),
+    ("exacto_dbfv_change_base_matrix", [_SZ, _U64, _U64, _U64, _SZ, _P], C.c_int),
+    ("exacto_dbfv_change_base", [_P, _SZ, _U64, _U64, _U64, _SZ, _P, _P, _SZ], C.c_int),
+    ("exacto_dbfv_change_base_dev", [_P, _SZ, _U64, _U64, _U64, _SZ, _P, _P, _SZ], C.c_int),
+    ("exacto_dbfv_div_by_base", [_P, _SZ, _U64, _U64, _P, _P, _SZ, C.POINTER(_U64)], C.c_int),
+    ("exacto_dbfv_div_by_base_dev", [_P, _SZ, _U64, _U64, _P, _P, _SZ, C.POINTER(_U64)], C.c_int),
     ("exacto_gen_secret_key", [_P, _P, _U64, _P], C.c_int),
     ("exacto_gen_secret_key_dev", [_P, _P, _U64, _P], C.c_int),
     ("exacto_gen_public_key", [_P, _P, C.c_double, _P, _U64, _P], C.c_int),
@@ -263,6 +280,13 @@ def required_trace_elements(n: int) -> list[int]:
     out = (C.c_uint64 * max(count, 1))()
     lib.exacto_required_trace_elements(n, out, count)
     return [int(v) for v in out[:count]]
+
+
+def dbfv_change_base_matrix(d: int, base: int, plain: int, new_base: int, new_d: int) -> np.ndarray:
+    """advanced.rs:119-130 (host-only entry point): [new_d][d], column i = digits of base^i mod p."""
+    out = np.zeros((max(new_d, 1), max(d, 1)), dtype=np.uint64)
+    check(load().exacto_dbfv_change_base_matrix(d, base, plain, new_base, new_d, out.ctypes.data))
+    return out[:new_d, :d]
 
 
 def _ptr(a) -> int | None:
@@ -472,6 +496,112 @@ class HipContext:
         check(self._lib.exacto_dbfv_decrypt_poly(self._h, d, base, plain, ct.ctypes.data, sk.ctypes.data,
                                                  out.ctypes.data, ct.shape[0]))
         return out
+
+    # ---- dBFV beyond the product (dbfv/encrypt.rs, eval.rs:11-71, keyswitch.rs, advanced.rs)
+    @staticmethod
+    def _depths(depth, B):
+        return np.ascontiguousarray(depth, dtype=np.uint32).reshape(B) if depth is not None else None
+
+    def _dbfv_encrypt(self, name, d, base, plain, src, keypoly, key, stream, sigma):
+        k, src, keypoly = self._key(key), _u64(src), _u64(keypoly)
+        B = src.shape[0]
+        ct = np.zeros((B, d, 2, self.L, self.n), dtype=np.uint64)
+        check(getattr(self._lib, name)(self._h, d, base, plain, src.ctypes.data, keypoly.ctypes.data, sigma,
+                                       k.ctypes.data, stream, ct.ctypes.data, B))
+        return ct
+
+    def dbfv_encrypt_sk(self, d, base, plain, values, sk, key, stream=0, sigma=3.2) -> np.ndarray:
+        """dbfv/encrypt.rs:73-81: values [B] scalars -> [B][d][2][L][n]."""
+        return self._dbfv_encrypt("exacto_dbfv_encrypt_sk", d, base, plain, _u64(values).reshape(-1), sk, key,
+                                  stream, sigma)
+
+    def dbfv_encrypt_pk(self, d, base, plain, values, pk, key, stream=0, sigma=3.2) -> np.ndarray:
+        """dbfv/encrypt.rs:27-35."""
+        return self._dbfv_encrypt("exacto_dbfv_encrypt_pk", d, base, plain, _u64(values).reshape(-1), pk, key,
+                                  stream, sigma)
+
+    def dbfv_encrypt_poly_sk(self, d, base, plain, pt, sk, key, stream=0, sigma=3.2) -> np.ndarray:
+        """dbfv/encrypt.rs:94-103: pt [B][n] mod p -> [B][d][2][L][n]."""
+        return self._dbfv_encrypt("exacto_dbfv_encrypt_poly_sk", d, base, plain, _u64(pt).reshape(-1, self.n), sk,
+                                  key, stream, sigma)
+
+    def dbfv_encrypt_poly_pk(self, d, base, plain, pt, pk, key, stream=0, sigma=3.2) -> np.ndarray:
+        """dbfv/encrypt.rs:51-60."""
+        return self._dbfv_encrypt("exacto_dbfv_encrypt_poly_pk", d, base, plain, _u64(pt).reshape(-1, self.n), pk,
+                                  key, stream, sigma)
+
+    def _dbfv_addsub(self, fn, a, b, depth_a, depth_b):
+        a, b = _u64(a), _u64(b)
+        B = a.shape[0]
+        out = np.zeros((B, a.shape[1], max(a.shape[2], b.shape[2]), self.L, self.n), dtype=np.uint64)
+        dout = np.zeros(B, dtype=np.uint32)
+        da, db = self._depths(depth_a, B), self._depths(depth_b, B)
+        check(fn(self._h, a.ctypes.data, a.shape[1], a.shape[2], b.ctypes.data, b.shape[1], b.shape[2],
+                 out.ctypes.data, B, _ptr(da), _ptr(db), dout.ctypes.data))
+        return out, dout
+
+    def dbfv_add(self, a, b, depth_a=None, depth_b=None):
+        """dbfv/eval.rs:11-33: a [B][d][p1][L][n] + b [B][d][p2][L][n] -> ([B][d][max][L][n], mul_depth [B])."""
+        return self._dbfv_addsub(self._lib.exacto_dbfv_add, a, b, depth_a, depth_b)
+
+    def dbfv_sub(self, a, b, depth_a=None, depth_b=None):
+        """dbfv/eval.rs:36-58."""
+        return self._dbfv_addsub(self._lib.exacto_dbfv_sub, a, b, depth_a, depth_b)
+
+    def dbfv_neg(self, ct) -> np.ndarray:
+        """dbfv/eval.rs:61-71."""
+        ct = _u64(ct)
+        out = np.zeros_like(ct)
+        check(self._lib.exacto_dbfv_neg(self._h, ct.ctypes.data, ct.shape[1], ct.shape[2], out.ctypes.data,
+                                        ct.shape[0]))
+        return out
+
+    def dbfv_relinearize(self, ct) -> np.ndarray:
+        """dbfv/keyswitch.rs:9-23 with the resident key: [B][d][3][L][n] -> [B][d][2][L][n]."""
+        ct = _u64(ct)
+        B, d, polys = ct.shape[:3]
+        out = np.zeros((B, d, polys if polys < 3 else 2, self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_dbfv_relinearize(self._h, ct.ctypes.data, d, polys, out.ctypes.data, B))
+        return out
+
+    def dbfv_apply_automorphism(self, ct, element, gk) -> np.ndarray:
+        """dbfv/advanced.rs:15-29: ct [B][d][2][L][n], gk [K][2][L][n]."""
+        ct, gk = _u64(ct), _u64(gk)
+        out = np.zeros_like(ct)
+        check(self._lib.exacto_dbfv_apply_automorphism(self._h, ct.ctypes.data, ct.shape[1], ct.shape[2], element,
+                                                       gk.ctypes.data if gk.size else None, gk.shape[0],
+                                                       out.ctypes.data, ct.shape[0]))
+        return out
+
+    def dbfv_linear_map(self, matrix, ct) -> np.ndarray:
+        """out[b][j] = sum_i ((matrix[j][i] mod t) mod q_l) in[b][i]: ct [B][d_in][polys][L][n], matrix
+        [d_out][d_in] -> [B][d_out][polys][L][n] (exacto_dbfv_linear_map)."""
+        ct = _u64(ct)
+        m = np.ascontiguousarray(np.array([[int(x) for x in row] for row in matrix], dtype=np.uint64))
+        d_out, d_in = m.shape
+        if d_in != ct.shape[1]:
+            raise ValueError(f"matrix has {d_in} columns, ciphertext {ct.shape[1]} limbs")
+        out = np.zeros((ct.shape[0], d_out) + ct.shape[2:], dtype=np.uint64)
+        check(self._lib.exacto_dbfv_linear_map(self._h, d_in, d_out, ct.shape[2], m.ctypes.data, ct.ctypes.data,
+                                               out.ctypes.data, ct.shape[0]))
+        return out
+
+    def dbfv_change_base(self, d, base, plain, new_base, new_d, ct) -> np.ndarray:
+        """dbfv/advanced.rs:99-160: ct [B][d][2][L][n] -> [B][new_d][2][L][n]."""
+        ct = _u64(ct)
+        out = np.zeros((ct.shape[0], max(new_d, 1), 2, self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_dbfv_change_base(self._h, d, base, plain, new_base, new_d, ct.ctypes.data,
+                                                out.ctypes.data, ct.shape[0]))
+        return out[:, :new_d]
+
+    def dbfv_div_by_base(self, d, base, plain, ct):
+        """dbfv/advanced.rs:36-93: (ct' [B][d][2][L][n], new plain modulus p / base)."""
+        ct = _u64(ct)
+        out = np.zeros_like(ct)
+        new_plain = C.c_uint64(0)
+        check(self._lib.exacto_dbfv_div_by_base(self._h, d, base, plain, ct.ctypes.data, out.ctypes.data,
+                                                ct.shape[0], C.byref(new_plain)))
+        return out, int(new_plain.value)
 
     # ---- key generation / encryption (keygen.rs:64-162, encrypt.rs:29-106); key = 4 u64 words
     @staticmethod
@@ -735,6 +865,58 @@ class HipContext:
         db = np.ascontiguousarray(depth_b, dtype=np.uint32) if depth_b is not None else None
         check(self._lib.exacto_dbfv_mul_dev(self._h, d, base, plain, self._p(a), self._p(b),
                                             self._p(out), batch, _ptr(da), _ptr(db), None))
+
+    def dbfv_encrypt_sk_dev(self, d, base, plain, values, sk, key, stream, ct, batch, sigma=3.2, poly=False):
+        """values [B] (poly: pt [B][n]) on the device -> ct [B][d][2][L][n]."""
+        fn = self._lib.exacto_dbfv_encrypt_poly_sk_dev if poly else self._lib.exacto_dbfv_encrypt_sk_dev
+        k = self._key(key)
+        check(fn(self._h, d, base, plain, self._p(values), self._p(sk), sigma, k.ctypes.data, stream, self._p(ct),
+                 batch))
+
+    def dbfv_encrypt_pk_dev(self, d, base, plain, values, pk, key, stream, ct, batch, sigma=3.2, poly=False):
+        fn = self._lib.exacto_dbfv_encrypt_poly_pk_dev if poly else self._lib.exacto_dbfv_encrypt_pk_dev
+        k = self._key(key)
+        check(fn(self._h, d, base, plain, self._p(values), self._p(pk), sigma, k.ctypes.data, stream, self._p(ct),
+                 batch))
+
+    def dbfv_add_dev(self, a, d1, polys1, b, d2, polys2, out, batch, depth_a=None, depth_b=None, sub=False):
+        """Returns mul_depth [B] of the results (exacto_dbfv_add_dev / exacto_dbfv_sub_dev)."""
+        fn = self._lib.exacto_dbfv_sub_dev if sub else self._lib.exacto_dbfv_add_dev
+        dout = np.zeros(batch, dtype=np.uint32)
+        da, db = self._depths(depth_a, batch), self._depths(depth_b, batch)
+        check(fn(self._h, self._p(a), d1, polys1, self._p(b), d2, polys2, self._p(out), batch, _ptr(da), _ptr(db),
+                 dout.ctypes.data))
+        return dout
+
+    def dbfv_sub_dev(self, a, d1, polys1, b, d2, polys2, out, batch, depth_a=None, depth_b=None):
+        return self.dbfv_add_dev(a, d1, polys1, b, d2, polys2, out, batch, depth_a, depth_b, sub=True)
+
+    def dbfv_neg_dev(self, ct, d, polys, out, batch):
+        check(self._lib.exacto_dbfv_neg_dev(self._h, self._p(ct), d, polys, self._p(out), batch))
+
+    def dbfv_relinearize_dev(self, ct, d, polys, out, batch):
+        check(self._lib.exacto_dbfv_relinearize_dev(self._h, self._p(ct), d, polys, self._p(out), batch))
+
+    def dbfv_apply_automorphism_dev(self, ct, d, element, gk, num_keys, out, batch):
+        check(self._lib.exacto_dbfv_apply_automorphism_dev(self._h, self._p(ct), d, 2, element, self._p(gk),
+                                                           num_keys, self._p(out), batch))
+
+    def dbfv_linear_map_dev(self, matrix, polys, ct, out, batch):
+        """matrix [d_out][d_in] on the host; ct, out device buffers (16-byte aligned, disjoint)."""
+        m = np.ascontiguousarray(np.array([[int(x) for x in row] for row in matrix], dtype=np.uint64))
+        check(self._lib.exacto_dbfv_linear_map_dev(self._h, m.shape[1], m.shape[0], polys, m.ctypes.data,
+                                                   self._p(ct), self._p(out), batch))
+
+    def dbfv_change_base_dev(self, d, base, plain, new_base, new_d, ct, out, batch):
+        check(self._lib.exacto_dbfv_change_base_dev(self._h, d, base, plain, new_base, new_d, self._p(ct),
+                                                    self._p(out), batch))
+
+    def dbfv_div_by_base_dev(self, d, base, plain, ct, out, batch) -> int:
+        """Returns the new plain modulus p / base."""
+        new_plain = C.c_uint64(0)
+        check(self._lib.exacto_dbfv_div_by_base_dev(self._h, d, base, plain, self._p(ct), self._p(out), batch,
+                                                    C.byref(new_plain)))
+        return int(new_plain.value)
 
     def dbfv_mul_limbs(self, d, base, plain, a: np.ndarray, b: np.ndarray, limbs) -> np.ndarray:
         """One GPU's output limbs of a split dbfv_mul: [B][len(limbs)][2][L][n], slot s = limb limbs[s]."""

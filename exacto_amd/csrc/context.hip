@@ -345,6 +345,9 @@ struct exacto_ctx {
     bool delta_ok = false;
     u64* enc_buf = nullptr;
     size_t enc_cap = 0;
+    u64* d_lin = nullptr;  // terms of the last dBFV linear map, LinTerm [E][L]
+    size_t lin_cap = 0;
+    std::vector<u64> lin_host;  // what d_lin holds
     u64* gk_s = nullptr;  // Shoup companions of the Galois key of the last automorphism call
     size_t gk_s_cap = 0;
     uint32_t* d_gk_rs = nullptr;  // ks32: Galois key of the last automorphism call in the 31-bit basis
@@ -1148,7 +1151,7 @@ extern "C" void exacto_ctx_destroy(exacto_ctx* c) {
         if (l.D16) (void)hipFree(l.D16);
     }
     free_dev(c->ext_a); free_dev(c->ext_b);
-    free_dev((u64*)c->d_cdt); free_dev(c->d_gpow); free_dev(c->d_delta); free_dev(c->enc_buf); free_dev(c->gk_s); free_dev(c->d_gk_rs); free_dev(c->d_dall); free_dev(c->d_hdig); free_dev(c->d_dk); free_dev(c->d_dsk); free_dev(c->d_uk); free_dev(c->pl_buf);
+    free_dev((u64*)c->d_cdt); free_dev(c->d_gpow); free_dev(c->d_delta); free_dev(c->enc_buf); free_dev(c->d_lin); free_dev(c->gk_s); free_dev(c->d_gk_rs); free_dev(c->d_dall); free_dev(c->d_hdig); free_dev(c->d_dk); free_dev(c->d_dsk); free_dev(c->d_uk); free_dev(c->pl_buf);
     if (c->ws_D16) (void)hipFree(c->ws_D16);
     free_dev(c->d_rs);   // the active basis' tables belong to kn / kz
     free_dev(c->kn.d_p32); free_dev(c->kn.d_tw32); free_dev(c->kn.d_kst); free_dev(c->kn.d_rs);
@@ -2901,39 +2904,56 @@ static int delta_residues(exacto_ctx* c) {
     return 0;
 }
 
+// The plaintexts of a dBFV encryption (dbfv/encrypt.rs:105-141): B scalars, or (poly) B polynomials
+// [B][n], each encrypted as its d base-`base` digit polynomials.
+struct DbfvPlain {
+    size_t d;
+    u64 base, plain;
+    bool poly;
+};
+
 // encrypt.rs:29-106 for a batch: pt = [B][n] plaintext coefficients, ct = [B][2][L][n] (NTT domain).
 // pk == nullptr: secret-key encryption with sk; otherwise public-key encryption with pk [2][L][n].
+// dp != nullptr: pt holds B dBFV plaintexts and the batch is their B * d digit encryptions, ct =
+// [B][d][2][L][n]: item b * d + k is what this function gives for digit plaintext k of item b; only
+// Delta*m is produced differently (straight from pt, and already in the NTT domain for scalars).
 static int encrypt_batch(exacto_ctx* c, const u64* pt, const u64* sk, const u64* pk, double sigma,
-                         const uint64_t* key, u64 stream, u64* ct, size_t B) {
+                         const uint64_t* key, u64 stream, u64* ct, size_t B, const DbfvPlain* dp = nullptr) {
     if (!key || !pt || !ct || (!sk && !pk)) return invalid_param("null argument");
-    if (B == 0) return 0;
+    const size_t items = dp ? B * dp->d : B;
+    if (items == 0) return 0;
     if (int e = delta_residues(c)) return e;
     const long Ln = (long)c->L * c->n;
     const ChaChaKey k = chacha_key(key);
-    // scratch: Delta m [B][L][n], and u [B][L][n] for pk-encryption
+    // scratch: Delta m [items][L][n], and u [items][L][n] for pk-encryption
     size_t cap = c->enc_cap;
-    if (grow(&c->enc_buf, &cap, (size_t)B * (pk ? 2 : 1) * Ln * sizeof(u64))) return EXACTO_ERR_HIP;
+    if (grow(&c->enc_buf, &cap, items * (pk ? 2 : 1) * Ln * sizeof(u64))) return EXACTO_ERR_HIP;
     c->enc_cap = cap;
     u64* dm = c->enc_buf;
-    u64* u = c->enc_buf + (size_t)B * Ln;
-    launch_scale_plain(pt, c->d_delta, dm, (long)B, c->n, c->L, c->d_primes, c->stream);
+    u64* u = c->enc_buf + items * Ln;
+    if (dp)
+        launch_dbfv_digits(pt, dp->poly, c->d_delta, dm, (long)B, (int)dp->d, dp->base, dp->plain, c->n, c->L,
+                           c->d_primes, c->stream);
+    else
+        launch_scale_plain(pt, c->d_delta, dm, (long)B, c->n, c->L, c->d_primes, c->stream);
     CHECK_LAUNCH();
-    if (int e = ntt_items(c, dm, (long)B, Ln, c->L)) return e;
+    if (!dp || dp->poly)
+        if (int e = ntt_items(c, dm, (long)items, Ln, c->L)) return e;
     if (!pk) {
         // encrypt.rs:79-106, item b: a (index 2b) -> c1, e (index 2b+1) -> c0 slot
-        if (int e = sample_polys(c, KG_UNIFORM, k, stream, ct + Ln, 2 * Ln, 0, 2, (long)B, sigma)) return e;
-        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct, 2 * Ln, 1, 2, (long)B, sigma)) return e;
-        if (int e = ntt_items(c, ct, (long)B, 2 * Ln, 2L * c->L)) return e;
-        launch_combine(KG_ENC_SK, ct, (long)B, 2 * Ln, Ln, sk, dm, nullptr, nullptr, nullptr, c->n, c->L, c->d_primes,
-                       c->stream);
+        if (int e = sample_polys(c, KG_UNIFORM, k, stream, ct + Ln, 2 * Ln, 0, 2, (long)items, sigma)) return e;
+        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct, 2 * Ln, 1, 2, (long)items, sigma)) return e;
+        if (int e = ntt_items(c, ct, (long)items, 2 * Ln, 2L * c->L)) return e;
+        launch_combine(KG_ENC_SK, ct, (long)items, 2 * Ln, Ln, sk, dm, nullptr, nullptr, nullptr, c->n, c->L,
+                       c->d_primes, c->stream);
     } else {
         // encrypt.rs:29-69, item b: u binary (3b), e1 (3b+1) -> c0 slot, e2 (3b+2) -> c1 slot
-        if (int e = sample_polys(c, KG_BINARY, k, stream, u, Ln, 0, 3, (long)B, sigma)) return e;
-        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct, 2 * Ln, 1, 3, (long)B, sigma)) return e;
-        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct + Ln, 2 * Ln, 2, 3, (long)B, sigma)) return e;
-        if (int e = ntt_items(c, u, (long)B, Ln, c->L)) return e;
-        if (int e = ntt_items(c, ct, (long)B, 2 * Ln, 2L * c->L)) return e;
-        launch_combine(KG_ENC_PK, ct, (long)B, 2 * Ln, Ln, nullptr, u, dm, pk, nullptr, c->n, c->L, c->d_primes,
+        if (int e = sample_polys(c, KG_BINARY, k, stream, u, Ln, 0, 3, (long)items, sigma)) return e;
+        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct, 2 * Ln, 1, 3, (long)items, sigma)) return e;
+        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct + Ln, 2 * Ln, 2, 3, (long)items, sigma)) return e;
+        if (int e = ntt_items(c, u, (long)items, Ln, c->L)) return e;
+        if (int e = ntt_items(c, ct, (long)items, 2 * Ln, 2L * c->L)) return e;
+        launch_combine(KG_ENC_PK, ct, (long)items, 2 * Ln, Ln, nullptr, u, dm, pk, nullptr, c->n, c->L, c->d_primes,
                        c->stream);
     }
     CHECK_LAUNCH();
@@ -3885,6 +3905,307 @@ extern "C" int exacto_encrypt_pk(exacto_ctx* c, const uint64_t* pt, const uint64
                      [&](std::vector<u64*>& d, u64* o) {
                          return exacto_encrypt_pk_dev(c, d[0], d[1], sigma, key, stream, o, B);
                      });
+}
+
+// ============================================================== dBFV beyond the product
+// encryption (dbfv/encrypt.rs), limb-wise operations (dbfv/eval.rs:11-71, dbfv/keyswitch.rs,
+// dbfv/advanced.rs:15-29) and the maps between digit vectors (dbfv/advanced.rs:36-160)
+
+static std::string u128_str(u128 v) {
+    std::string s;
+    do { s.insert(s.begin(), char('0' + (int)(v % 10))); v /= 10; } while (v);
+    return s;
+}
+
+// DbfvParams::new, then validate_digit_polys' base check (dbfv/encrypt.rs:152-159; its coefficient
+// check cannot fail: digits are below base <= t), then normalize_poly_plaintext's (encrypt.rs:121-126)
+static int dbfv_encrypt_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* src, bool poly,
+                            const uint64_t* sk, const uint64_t* pk, double sigma, const uint64_t* key,
+                            uint64_t stream, uint64_t* ct, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = dbfv_params_check(d, base, plain)) return e;
+    if (poly && plain == 0)
+        return invalid_param("polynomial dBFV plaintext requires finite plain_modulus (plain_modulus=0 is scalar-only)");
+    if (base > c->plain)
+        return invalid_param("dBFV base " + std::to_string(base) + " must be <= BFV plaintext modulus " +
+                             std::to_string(c->plain));
+    if (!sk && !pk) return invalid_param("null argument");
+    if (d > (size_t)INT32_MAX / 2 || B > (size_t)INT32_MAX / d) return invalid_param("batch * num_digits too large");
+    const DbfvPlain dp{d, base, plain, poly};
+    return encrypt_batch(c, src, sk, pk, sigma, key, stream, ct, B, &dp);
+}
+
+static int dbfv_encrypt_host(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* src, bool poly,
+                             const uint64_t* sk, const uint64_t* pk, double sigma, const uint64_t* key,
+                             uint64_t stream, uint64_t* ct, size_t B) {
+    if (!c) return invalid_param("null context");
+    const size_t keyb = (pk ? 2 : 1) * c->L * poly_bytes(c);
+    return host_call(c, {{src, poly ? B * poly_bytes(c) : B * sizeof(u64)}, {pk ? pk : sk, keyb}},
+                     B * d * 2 * c->L * poly_bytes(c), ct, [&](std::vector<u64*>& in, u64* o) {
+                         return dbfv_encrypt_dev(c, d, base, plain, in[0], poly, pk ? nullptr : in[1],
+                                                 pk ? in[1] : nullptr, sigma, key, stream, o, B);
+                     });
+}
+
+extern "C" int exacto_dbfv_encrypt_sk_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                          const uint64_t* values, const uint64_t* sk, double sigma,
+                                          const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (!sk) return invalid_param("null argument");
+    return dbfv_encrypt_dev(c, d, base, plain, values, false, sk, nullptr, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_dbfv_encrypt_pk_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                          const uint64_t* values, const uint64_t* pk, double sigma,
+                                          const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (!pk) return invalid_param("null argument");
+    return dbfv_encrypt_dev(c, d, base, plain, values, false, nullptr, pk, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_dbfv_encrypt_poly_sk_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                               const uint64_t* pt, const uint64_t* sk, double sigma,
+                                               const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (!sk) return invalid_param("null argument");
+    return dbfv_encrypt_dev(c, d, base, plain, pt, true, sk, nullptr, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_dbfv_encrypt_poly_pk_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                               const uint64_t* pt, const uint64_t* pk, double sigma,
+                                               const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (!pk) return invalid_param("null argument");
+    return dbfv_encrypt_dev(c, d, base, plain, pt, true, nullptr, pk, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_dbfv_encrypt_sk(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* values,
+                                      const uint64_t* sk, double sigma, const uint64_t* key, uint64_t stream,
+                                      uint64_t* ct, size_t B) {
+    if (!sk) return invalid_param("null argument");
+    return dbfv_encrypt_host(c, d, base, plain, values, false, sk, nullptr, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_dbfv_encrypt_pk(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* values,
+                                      const uint64_t* pk, double sigma, const uint64_t* key, uint64_t stream,
+                                      uint64_t* ct, size_t B) {
+    if (!pk) return invalid_param("null argument");
+    return dbfv_encrypt_host(c, d, base, plain, values, false, nullptr, pk, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_dbfv_encrypt_poly_sk(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* pt,
+                                           const uint64_t* sk, double sigma, const uint64_t* key, uint64_t stream,
+                                           uint64_t* ct, size_t B) {
+    if (!sk) return invalid_param("null argument");
+    return dbfv_encrypt_host(c, d, base, plain, pt, true, sk, nullptr, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_dbfv_encrypt_poly_pk(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* pt,
+                                           const uint64_t* pk, double sigma, const uint64_t* key, uint64_t stream,
+                                           uint64_t* ct, size_t B) {
+    if (!pk) return invalid_param("null argument");
+    return dbfv_encrypt_host(c, d, base, plain, pt, true, nullptr, pk, sigma, key, stream, ct, B);
+}
+
+// dbfv_add / dbfv_sub (dbfv/eval.rs:11-58): the limbs are B * d independent BFV ciphertexts
+static int dbfv_addsub_dev(exacto_ctx* c, bool sub, const uint64_t* a, size_t d1, size_t p1, const uint64_t* b,
+                           size_t d2, size_t p2, uint64_t* out, size_t B, const uint32_t* da, const uint32_t* db,
+                           uint32_t* dout) {
+    if (int e = check_ctx(c)) return e;
+    if (d1 != d2)
+        return fail(EXACTO_ERR_DIMENSION_MISMATCH,
+                    "dimension mismatch: expected " + std::to_string(d1) + ", got " + std::to_string(d2));
+    if (int e = bfv_addsub(c, sub, a, p1, b, p2, out, B * d1)) return e;
+    if (dout)
+        for (size_t i = 0; i < B; ++i) dout[i] = std::max(da ? da[i] : 0u, db ? db[i] : 0u);
+    return 0;
+}
+static int dbfv_addsub_host(exacto_ctx* c, bool sub, const uint64_t* a, size_t d1, size_t p1, const uint64_t* b,
+                            size_t d2, size_t p2, uint64_t* out, size_t B, const uint32_t* da, const uint32_t* db,
+                            uint32_t* dout) {
+    if (!c) return invalid_param("null context");
+    if (d1 != d2) return dbfv_addsub_dev(c, sub, a, d1, p1, b, d2, p2, out, B, da, db, dout);
+    const size_t pb = c->L * poly_bytes(c);
+    return host_call(c, {{a, B * d1 * p1 * pb}, {b, B * d2 * p2 * pb}}, B * d1 * std::max(p1, p2) * pb, out,
+                     [&](std::vector<u64*>& in, u64* o) {
+                         return dbfv_addsub_dev(c, sub, in[0], d1, p1, in[1], d2, p2, o, B, da, db, dout);
+                     });
+}
+extern "C" int exacto_dbfv_add_dev(exacto_ctx* c, const uint64_t* a, size_t d1, size_t p1, const uint64_t* b, size_t d2,
+                                   size_t p2, uint64_t* out, size_t B, const uint32_t* da, const uint32_t* db,
+                                   uint32_t* dout) {
+    return dbfv_addsub_dev(c, false, a, d1, p1, b, d2, p2, out, B, da, db, dout);
+}
+extern "C" int exacto_dbfv_sub_dev(exacto_ctx* c, const uint64_t* a, size_t d1, size_t p1, const uint64_t* b, size_t d2,
+                                   size_t p2, uint64_t* out, size_t B, const uint32_t* da, const uint32_t* db,
+                                   uint32_t* dout) {
+    return dbfv_addsub_dev(c, true, a, d1, p1, b, d2, p2, out, B, da, db, dout);
+}
+extern "C" int exacto_dbfv_add(exacto_ctx* c, const uint64_t* a, size_t d1, size_t p1, const uint64_t* b, size_t d2,
+                               size_t p2, uint64_t* out, size_t B, const uint32_t* da, const uint32_t* db,
+                               uint32_t* dout) {
+    return dbfv_addsub_host(c, false, a, d1, p1, b, d2, p2, out, B, da, db, dout);
+}
+extern "C" int exacto_dbfv_sub(exacto_ctx* c, const uint64_t* a, size_t d1, size_t p1, const uint64_t* b, size_t d2,
+                               size_t p2, uint64_t* out, size_t B, const uint32_t* da, const uint32_t* db,
+                               uint32_t* dout) {
+    return dbfv_addsub_host(c, true, a, d1, p1, b, d2, p2, out, B, da, db, dout);
+}
+
+// dbfv_neg (eval.rs:61-71), dbfv_relinearize (keyswitch.rs:9-23), dbfv_apply_automorphism
+// (advanced.rs:15-29): the BFV entry point over the B * d limbs
+extern "C" int exacto_dbfv_neg_dev(exacto_ctx* c, const uint64_t* ct, size_t d, size_t polys, uint64_t* out, size_t B) {
+    return exacto_bfv_neg_dev(c, ct, polys, out, B * d);
+}
+extern "C" int exacto_dbfv_neg(exacto_ctx* c, const uint64_t* ct, size_t d, size_t polys, uint64_t* out, size_t B) {
+    return exacto_bfv_neg(c, ct, polys, out, B * d);
+}
+extern "C" int exacto_dbfv_relinearize_dev(exacto_ctx* c, const uint64_t* ct, size_t d, size_t polys, uint64_t* out,
+                                           size_t B) {
+    return exacto_relinearize_dev(c, ct, polys, out, B * d);
+}
+extern "C" int exacto_dbfv_relinearize(exacto_ctx* c, const uint64_t* ct, size_t d, size_t polys, uint64_t* out,
+                                       size_t B) {
+    return exacto_relinearize(c, ct, polys, out, B * d);
+}
+extern "C" int exacto_dbfv_apply_automorphism_dev(exacto_ctx* c, const uint64_t* ct, size_t d, size_t polys,
+                                                  uint64_t element, const uint64_t* gk, size_t num_keys, uint64_t* out,
+                                                  size_t B) {
+    return exacto_bfv_apply_automorphism_dev(c, ct, polys, element, gk, num_keys, out, B * d);
+}
+extern "C" int exacto_dbfv_apply_automorphism(exacto_ctx* c, const uint64_t* ct, size_t d, size_t polys,
+                                              uint64_t element, const uint64_t* gk, size_t num_keys, uint64_t* out,
+                                              size_t B) {
+    return exacto_bfv_apply_automorphism(c, ct, polys, element, gk, num_keys, out, B * d);
+}
+
+// out[b][j] = sum_i ((matrix[j][i] mod t) mod q_l) * in[b][i]: bfv_scalar_plain_mul (advanced.rs:162-171:
+// the scalar mod t as a constant plaintext, whose lift is the same residue in every slot) and bfv_add.
+extern "C" int exacto_dbfv_linear_map_dev(exacto_ctx* c, size_t d_in, size_t d_out, size_t polys,
+                                          const uint64_t* matrix, const uint64_t* in, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (d_in < 1 || d_out < 1) return invalid_param("num_digits must be >= 1");
+    if (d_in > 4096 || d_out > 4096) return invalid_param("linear map larger than 4096 digits");
+    if (!matrix) return invalid_param("null matrix");
+    if (B == 0 || polys == 0) return 0;
+    if (!in || !out) return invalid_param("null ciphertext pointer");
+    const size_t limb = polys * c->L * (size_t)c->n;
+    if (in < out + B * d_out * limb && out < in + B * d_in * limb)
+        return invalid_param("linear map output must not overlap its input");
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return invalid_param("linear map buffers must be 16-byte aligned");
+    if (B * polys * c->L > ((size_t)1 << 31) / c->n * 256) return invalid_param("batch too large");
+    // the non-zero entries row by row (the reference skips a zero coefficient, advanced.rs:138-140),
+    // reduced per limb; a row without any is one empty term, so that every output limb is written
+    const int L = c->L;
+    std::vector<u64> tab;
+    size_t E = 0;
+    auto term = [&](u64 m, size_t col, bool last) {
+        for (int l = 0; l < L; ++l) {
+            const u64 q = c->primes[l], s = m % q;
+            const u64 w[4] = {s, shoup_h(s, q), (u64)col | ((u64)(last ? 1 : 0) << 32), 0};
+            tab.insert(tab.end(), w, w + 4);
+        }
+        ++E;
+    };
+    for (size_t j = 0; j < d_out; ++j) {
+        size_t last_nz = d_in;
+        for (size_t i = 0; i < d_in; ++i)
+            if (matrix[j * d_in + i] % c->plain) last_nz = i;
+        if (last_nz == d_in) term(0, 0, true);
+        for (size_t i = 0; i <= last_nz && last_nz < d_in; ++i)
+            if (const u64 m = matrix[j * d_in + i] % c->plain) term(m, i, i == last_nz);
+    }
+    static_assert(sizeof(LinTerm) == 4 * sizeof(u64), "LinTerm is four words: s, ss, {col, last}, pad");
+    if (tab != c->lin_host) {  // the same map again (a circuit's repeated step): the resident table stands
+        // the table is host-pageable and d_lin may still be read by a previous call's kernel
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->lin_host.clear();
+        size_t cap = c->lin_cap;
+        if (grow(&c->d_lin, &cap, tab.size() * sizeof(u64))) return EXACTO_ERR_HIP;
+        c->lin_cap = cap;
+        if (int e_ = upload(c, c->d_lin, tab.data(), tab.size() * sizeof(u64))) return e_;
+        c->lin_host = tab;
+    }
+    launch_dbfv_linmap(in, out, reinterpret_cast<const LinTerm*>(c->d_lin), (int)E, (int)d_in, (int)d_out, (long)B,
+                       (int)polys, c->n, L, c->d_primes, c->stream);
+    CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int exacto_dbfv_linear_map(exacto_ctx* c, size_t d_in, size_t d_out, size_t polys, const uint64_t* matrix,
+                                      const uint64_t* in, uint64_t* out, size_t B) {
+    if (!c) return invalid_param("null context");
+    const size_t lb = polys * c->L * poly_bytes(c);
+    return host_call(c, {{in, B * d_in * lb}}, B * d_out * lb, out, [&](std::vector<u64*>& dv, u64* o) {
+        return exacto_dbfv_linear_map_dev(c, d_in, d_out, polys, matrix, dv[0], o, B);
+    });
+}
+
+// advanced.rs:104-130, 147-152: M[j][i] = digit j of (base^i mod p) in base new_base
+static int change_base_matrix(size_t d, uint64_t base, uint64_t plain, uint64_t new_base, size_t new_d,
+                              std::vector<u64>* M) {
+    if (int e = dbfv_params_check(d, base, plain)) return e;
+    if (new_base < 2) return invalid_param("new base must be >= 2");
+    if (new_d == 0) return invalid_param("new_num_digits must be >= 1");
+    if (int e = dbfv_params_check(new_d, new_base, plain)) return e;
+    if (d > 4096 || new_d > 4096) return invalid_param("linear map larger than 4096 digits");
+    M->assign(new_d * d, 0);
+    u128 b_pow = 1;  // p = 2^64: the reduction is the truncation to 64 bits
+    for (size_t i = 0; i < d; ++i) {
+        u64 rem = plain ? (u64)(b_pow % plain) : (u64)b_pow;
+        for (size_t j = 0; j < new_d; ++j) {
+            (*M)[j * d + i] = rem % new_base;
+            rem /= new_base;
+        }
+        b_pow = plain ? (b_pow * base) % plain : (u128)(u64)((u64)b_pow * base);
+    }
+    return 0;
+}
+
+extern "C" int exacto_dbfv_change_base_matrix(size_t d, uint64_t base, uint64_t plain, uint64_t new_base, size_t new_d,
+                                              uint64_t* out) {
+    std::vector<u64> M;
+    if (int e = change_base_matrix(d, base, plain, new_base, new_d, &M)) return e;
+    if (!out) return invalid_param("null matrix");
+    std::memcpy(out, M.data(), M.size() * sizeof(u64));
+    return 0;
+}
+
+extern "C" int exacto_dbfv_change_base_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, uint64_t new_base,
+                                           size_t new_d, const uint64_t* in, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    std::vector<u64> M;
+    if (int e = change_base_matrix(d, base, plain, new_base, new_d, &M)) return e;
+    return exacto_dbfv_linear_map_dev(c, d, new_d, 2, M.data(), in, out, B);
+}
+
+extern "C" int exacto_dbfv_change_base(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, uint64_t new_base,
+                                       size_t new_d, const uint64_t* in, uint64_t* out, size_t B) {
+    if (!c) return invalid_param("null context");
+    const size_t lb = 2 * c->L * poly_bytes(c);
+    return host_call(c, {{in, B * d * lb}}, B * new_d * lb, out, [&](std::vector<u64*>& dv, u64* o) {
+        return exacto_dbfv_change_base_dev(c, d, base, plain, new_base, new_d, dv[0], o, B);
+    });
+}
+
+// advanced.rs:36-93: phi_b as a matrix: row 0 = (base^-1 mod t, 1, 0, ...), row i = e_{i+1}, last row 0
+extern "C" int exacto_dbfv_div_by_base_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* in,
+                                           uint64_t* out, size_t B, uint64_t* new_plain) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = dbfv_params_check(d, base, plain)) return e;
+    if (d > 4096) return invalid_param("linear map larger than 4096 digits");
+    const u64 inv = invmod_h(base % c->plain, c->plain);
+    if (inv == 0) return invalid_param("base not invertible modulo BFV plaintext modulus");
+    const u128 old_p = plain == 0 ? ((u128)1 << 64) : (u128)plain;
+    if (old_p % base != 0)
+        return invalid_param("plaintext modulus " + u128_str(old_p) + " is not divisible by base " +
+                             std::to_string(base));
+    const u64 np = (u64)(old_p / base);  // base >= 2: below 2^64
+    if (int e = dbfv_params_check(d, base, np)) return e;
+    std::vector<u64> M(d * d, 0);
+    M[0] = inv;
+    for (size_t i = 0; i + 1 < d; ++i) M[i * d + i + 1] = 1;
+    if (int e = exacto_dbfv_linear_map_dev(c, d, d, 2, M.data(), in, out, B)) return e;
+    if (new_plain) *new_plain = np;
+    return 0;
+}
+
+extern "C" int exacto_dbfv_div_by_base(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* in,
+                                       uint64_t* out, size_t B, uint64_t* new_plain) {
+    if (!c) return invalid_param("null context");
+    const size_t bytes = B * d * 2 * c->L * poly_bytes(c);
+    return host_call(c, {{in, bytes}}, bytes, out, [&](std::vector<u64*>& dv, u64* o) {
+        return exacto_dbfv_div_by_base_dev(c, d, base, plain, dv[0], o, B, new_plain);
+    });
 }
 
 // ============================================================== diagnostics

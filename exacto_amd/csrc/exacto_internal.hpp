@@ -278,6 +278,23 @@ void launch_scale_plain(const u64* pt, const u64* delta, u64* dm, long items, in
 void launch_combine(int op, u64* x, long items, long item_stride, long x1_off, const u64* s, const u64* aux,
                     const u64* aux2, const u64* pk, const u64* gpow, int n, int L, const PrimeConst* primes,
                     hipStream_t st);
+// dBFV plaintexts -> Delta*m rows dm [items * d][L][n]: src = values [items] (rows in the NTT domain: constant
+// polynomials) or, poly, pt [items][n] (rows in the coefficient domain); p == 0: 2^64
+void launch_dbfv_digits(const u64* src, bool poly, const u64* delta, u64* dm, long items, int d, u64 base, u64 p, int n,
+                        int L, const PrimeConst* primes, hipStream_t s);
+
+// ---- linear maps between dBFV digit vectors (dbfv_linear.hip) ----
+// One non-zero entry of the matrix for one limb l: s = (m_ji mod t) mod q_l with its Shoup companion,
+// col = i, last = 1 on the final term of output limb j.  A row of zeros is one term with s = 0.
+struct __attribute__((aligned(32))) LinTerm {
+    u64 s, ss;
+    int col, last;
+    u64 pad_;
+};
+// out[b][j] = sum of row j's terms per component, limb l and slot; in [items][d_in][polys][L][n], out
+// [items][d_out][polys][L][n], both 16-byte aligned and disjoint; terms [E][L], rows in order, d_out lasts
+void launch_dbfv_linmap(const u64* in, u64* out, const LinTerm* terms, int E, int d_in, int d_out, long items,
+                        int polys, int n, int L, const PrimeConst* primes, hipStream_t s);
 
 // ---- plaintext-ciphertext operations (plain.hip) ----
 enum { PLAIN_MUL = 0, PLAIN_ADD = 1 };

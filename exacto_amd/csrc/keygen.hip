@@ -141,6 +141,90 @@ void launch_scale_plain(const u64* pt, const u64* delta, u64* dm, long items, in
     EXACTO_LAUNCH(scale_plain_kernel, dim3((unsigned)blocks), dim3(KG_TPB), 0, s, pt, delta, dm, n, L, primes);
 }
 
+// dBFV plaintexts (dbfv/encrypt.rs:105-141 + decomposition.rs:8-16 + bfv/encrypt.rs:181-201) fused:
+// reduce mod p (p == 0: 2^64, taken as is), digit k in base b, times Delta_i mod q_i, written as the
+// Delta*m rows [b * d + k][i][n] of the B * d limb encryptions; the digit plaintexts themselves never
+// exist in memory.  shift >= 0: b = 2^shift (shift and mask), otherwise a 64-bit divide per digit.
+__device__ __forceinline__ u64 dbfv_digit_next(u64& v, u64 base, int shift) {
+    u64 dg;
+    if (shift >= 0) {
+        dg = v & (base - 1);
+        v >>= shift;
+    } else {
+        const u64 qt = v / base;
+        dg = v - qt * base;
+        v = qt;
+    }
+    return dg;
+}
+
+// Scalar plaintexts: the digit polynomial is a constant, whose NTT is that constant in every slot
+// (as trivial_const_kernel), so the rows are written in the NTT domain.  One block per row chunk:
+// the row's constant is computed once per thread and stored to 2 adjacent slots per pass.
+static constexpr int DG_PASSES = 4;
+__global__ void __launch_bounds__(KG_TPB)
+dbfv_digits_const_kernel(const u64* __restrict__ values, const u64* __restrict__ delta, u64* __restrict__ dm, int d,
+                         u64 base, int shift, u64 p, int n, int L, const PrimeConst* __restrict__ primes) {
+    const int span = 2 * KG_TPB * DG_PASSES;
+    const int nblk = (n + span - 1) / span;
+    const long row = blockIdx.x / nblk;  // row = (b * d + k) * L + i
+    const int j0 = (int)(blockIdx.x - row * nblk) * span + 2 * (int)threadIdx.x;
+    const int i = (int)(row % L);
+    const long limb = row / L;
+    const long b = limb / d;
+    const int k = (int)(limb - b * d);
+    u64 v = values[b];
+    if (p) v %= p;
+    u64 dg = 0;
+    for (int t = 0; t <= k; ++t) dg = dbfv_digit_next(v, base, shift);
+    const PrimeConst& P = primes[i];
+    const u64 c = mul_mod(reduce64(dg, P.q, P.mu64), delta[i], P);
+    ulonglong2 cc;
+    cc.x = c;
+    cc.y = c;
+#pragma unroll
+    for (int t = 0; t < DG_PASSES; ++t) {
+        const int j = j0 + t * 2 * KG_TPB;
+        if (j < n) *reinterpret_cast<ulonglong2*>(dm + row * n + j) = cc;  // n even: j + 1 < n
+    }
+}
+
+// Polynomial plaintexts: one thread per (item, coefficient) reads pt once and writes its d * L
+// residues, coefficient domain (the forward transforms follow as for any plaintext).
+__global__ void __launch_bounds__(KG_TPB)
+dbfv_digits_poly_kernel(const u64* __restrict__ pt, const u64* __restrict__ delta, u64* __restrict__ dm, int d,
+                        u64 base, int shift, u64 p, int n, int L, const PrimeConst* __restrict__ primes) {
+    const int nblk = (n + KG_TPB - 1) / KG_TPB;
+    const long b = blockIdx.x / nblk;
+    const int j = (int)(blockIdx.x - b * nblk) * KG_TPB + threadIdx.x;
+    if (j >= n) return;
+    u64 v = pt[b * n + j];
+    if (p) v %= p;
+    for (int k = 0; k < d; ++k) {
+        const u64 dg = dbfv_digit_next(v, base, shift);
+        for (int i = 0; i < L; ++i) {
+            const PrimeConst& P = primes[i];
+            dm[((b * d + k) * L + i) * n + j] = mul_mod(reduce64(dg, P.q, P.mu64), delta[i], P);
+        }
+    }
+}
+
+void launch_dbfv_digits(const u64* src, bool poly, const u64* delta, u64* dm, long items, int d, u64 base, u64 p, int n,
+                        int L, const PrimeConst* primes, hipStream_t s) {
+    if (items == 0 || d == 0) return;
+    const int shift = (base & (base - 1)) == 0 ? __builtin_ctzll(base) : -1;
+    if (poly) {
+        const long blocks = items * ((n + KG_TPB - 1) / KG_TPB);
+        EXACTO_LAUNCH(dbfv_digits_poly_kernel, dim3((unsigned)blocks), dim3(KG_TPB), 0, s, src, delta, dm, d, base,
+                      shift, p, n, L, primes);
+    } else {
+        const int span = 2 * KG_TPB * DG_PASSES;
+        const long blocks = items * d * L * ((n + span - 1) / span);
+        EXACTO_LAUNCH(dbfv_digits_const_kernel, dim3((unsigned)blocks), dim3(KG_TPB), 0, s, src, delta, dm, d, base,
+                      shift, p, n, L, primes);
+    }
+}
+
 // NTT-domain combinations, one thread per (item, limb, coefficient); polynomials [L][n] per item.
 //   KG_RLK : x0 <- -(x1*s + x0) + s^2 * base^key  (rlk_i = (-(a_i s + e_i) + g_i s^2, a_i): x0 holds e_i,
 //            x1 holds a_i; gpow[key * L + i] = base^key mod q_i)                       keygen.rs:137-155

@@ -743,6 +743,190 @@ inline CoeffPoly dbfv_decrypt_poly(const DbfvCiphertext& ct, const SecretKey& sk
     return res;
 }
 
+// ---- exacto::dbfv beyond the product: keygen, encrypt, eval, keyswitch, advanced
+using DbfvParamsPtr = std::shared_ptr<const DbfvParams>;
+
+// dbfv_keygen / dbfv_keygen_full (src/dbfv/keygen.rs:9-30) with the caller's RNG, as every
+// generator of this header takes it.
+struct DbfvKeys {
+    SecretKey sk;
+    PublicKey pk;
+    RelinKey rlk;
+    std::vector<GaloisKey> gks;
+};
+inline DbfvKeys dbfv_keygen_full(const DbfvParamsPtr& params, const std::vector<size_t>& galois_elements,
+                                 ChaChaRng& rng) {
+    DbfvKeys k;
+    k.sk = gen_secret_key_with_rng(params->bfv_params, rng);
+    k.pk = gen_public_key_with_rng(k.sk, rng);
+    k.rlk = gen_relin_key_with_rng(k.sk, rng);
+    for (size_t e : galois_elements) k.gks.push_back(gen_galois_key_with_rng(k.sk, e, rng));
+    return k;
+}
+inline DbfvKeys dbfv_keygen(const DbfvParamsPtr& params, ChaChaRng& rng) { return dbfv_keygen_full(params, {}, rng); }
+
+namespace detail {
+inline DbfvCiphertext make_dbfv(const std::vector<uint64_t>& flat, size_t d, size_t polys, size_t degree,
+                                size_t mul_depth, const DbfvParamsPtr& params) {
+    DbfvCiphertext res;
+    res.limbs = unflatten(flat, d, polys, params->bfv_params);
+    res.degree = degree;
+    res.mul_depth = mul_depth;
+    res.params = params;
+    return res;
+}
+inline size_t dbfv_polys(const DbfvCiphertext& ct) {
+    if (ct.limbs.empty()) throw ExactoError(1, "invalid parameter: empty dBFV ciphertext");
+    return ct.limbs[0].c.size();
+}
+inline size_t limb_words(const DbfvParams& dp) { return dp.bfv_params->num_limbs() * dp.bfv_params->ring_degree; }
+inline DbfvCiphertext dbfv_encrypt_any(const uint64_t* src, bool poly, const SecretKey* sk, const PublicKey* pk,
+                                       const DbfvParamsPtr& params, ChaChaRng& rng) {
+    const DbfvParams& dp = *params;
+    const BfvParams& prm = *dp.bfv_params;
+    const size_t d = dp.num_digits;
+    std::vector<uint64_t> ct(d * 2 * limb_words(dp));
+    std::vector<uint64_t> pkf;
+    if (pk) {
+        pkf = pk->pk0.data;
+        pkf.insert(pkf.end(), pk->pk1.data.begin(), pk->pk1.data.end());
+    }
+    auto fn = sk ? (poly ? exacto_dbfv_encrypt_poly_sk : exacto_dbfv_encrypt_sk)
+                 : (poly ? exacto_dbfv_encrypt_poly_pk : exacto_dbfv_encrypt_pk);
+    check(fn(prm.ctx(), d, dp.base, dp.plain_modulus, src, sk ? sk->poly.data.data() : pkf.data(), prm.sigma,
+             rng.key, rng.next(), ct.data(), 1));
+    return make_dbfv(ct, d, 2, d, 0, params);  // degree = num_digits, mul_depth = 0 (encrypt.rs:196-201)
+}
+inline const uint64_t* poly_plain(const CoeffPoly& pt, const DbfvParams& dp) {
+    // normalize_poly_plaintext (dbfv/encrypt.rs:120-141); the p = 2^64 error is the library's
+    if (dp.plain_modulus != 0) {
+        const size_t n = dp.bfv_params->ring_degree;
+        if (pt.coeffs.size() != n)
+            throw ExactoError(2, "dimension mismatch: expected " + std::to_string(n) + ", got " +
+                                     std::to_string(pt.coeffs.size()));
+        if (pt.modulus != dp.plain_modulus) throw ExactoError(3, "modulus mismatch");
+    }
+    return pt.coeffs.data();
+}
+}  // namespace detail
+
+// dbfv_encrypt_with_rng / dbfv_encrypt_sk_with_rng (src/dbfv/encrypt.rs:27-35, 73-81)
+inline DbfvCiphertext dbfv_encrypt_with_rng(uint64_t plaintext, const PublicKey& pk, const DbfvParamsPtr& params,
+                                            ChaChaRng& rng) {
+    return detail::dbfv_encrypt_any(&plaintext, false, nullptr, &pk, params, rng);
+}
+inline DbfvCiphertext dbfv_encrypt_sk_with_rng(uint64_t plaintext, const SecretKey& sk, const DbfvParamsPtr& params,
+                                               ChaChaRng& rng) {
+    return detail::dbfv_encrypt_any(&plaintext, false, &sk, nullptr, params, rng);
+}
+// dbfv_encrypt_poly_with_rng / dbfv_encrypt_poly_sk_with_rng (src/dbfv/encrypt.rs:51-60, 94-103)
+inline DbfvCiphertext dbfv_encrypt_poly_with_rng(const CoeffPoly& pt, const PublicKey& pk, const DbfvParamsPtr& params,
+                                                 ChaChaRng& rng) {
+    return detail::dbfv_encrypt_any(detail::poly_plain(pt, *params), true, nullptr, &pk, params, rng);
+}
+inline DbfvCiphertext dbfv_encrypt_poly_sk_with_rng(const CoeffPoly& pt, const SecretKey& sk,
+                                                    const DbfvParamsPtr& params, ChaChaRng& rng) {
+    return detail::dbfv_encrypt_any(detail::poly_plain(pt, *params), true, &sk, nullptr, params, rng);
+}
+// the reference's names without `_with_rng` draw from the OS; here the RNG is always the caller's
+inline DbfvCiphertext dbfv_encrypt_pk(uint64_t m, const PublicKey& pk, const DbfvParamsPtr& p, ChaChaRng& rng) {
+    return dbfv_encrypt_with_rng(m, pk, p, rng);
+}
+inline DbfvCiphertext dbfv_encrypt_sk(uint64_t m, const SecretKey& sk, const DbfvParamsPtr& p, ChaChaRng& rng) {
+    return dbfv_encrypt_sk_with_rng(m, sk, p, rng);
+}
+inline DbfvCiphertext dbfv_encrypt_poly_pk(const CoeffPoly& pt, const PublicKey& pk, const DbfvParamsPtr& p,
+                                           ChaChaRng& rng) {
+    return dbfv_encrypt_poly_with_rng(pt, pk, p, rng);
+}
+inline DbfvCiphertext dbfv_encrypt_poly_sk(const CoeffPoly& pt, const SecretKey& sk, const DbfvParamsPtr& p,
+                                           ChaChaRng& rng) {
+    return dbfv_encrypt_poly_sk_with_rng(pt, sk, p, rng);
+}
+
+namespace detail {
+inline DbfvCiphertext dbfv_addsub(bool sub, const DbfvCiphertext& a, const DbfvCiphertext& b) {
+    const DbfvParams& dp = *a.params;
+    const size_t d1 = a.num_limbs(), d2 = b.num_limbs();
+    const size_t p1 = d1 ? a.limbs[0].c.size() : 0, p2 = d2 ? b.limbs[0].c.size() : 0, pm = std::max(p1, p2);
+    auto fa = flatten(a.limbs, p1), fb = flatten(b.limbs, p2);
+    std::vector<uint64_t> out(d1 * pm * limb_words(dp));
+    const uint32_t da = (uint32_t)a.mul_depth, db = (uint32_t)b.mul_depth;
+    uint32_t dout = 0;
+    check((sub ? exacto_dbfv_sub : exacto_dbfv_add)(dp.bfv_params->ctx(), fa.data(), d1, p1, fb.data(), d2, p2,
+                                                    out.data(), 1, &da, &db, &dout));
+    return make_dbfv(out, d1, pm, std::max(a.degree, b.degree), dout, a.params);  // eval.rs:27-32
+}
+}  // namespace detail
+
+// dbfv_add / dbfv_sub / dbfv_neg (src/dbfv/eval.rs:11-71)
+inline DbfvCiphertext dbfv_add(const DbfvCiphertext& a, const DbfvCiphertext& b) {
+    return detail::dbfv_addsub(false, a, b);
+}
+inline DbfvCiphertext dbfv_sub(const DbfvCiphertext& a, const DbfvCiphertext& b) {
+    return detail::dbfv_addsub(true, a, b);
+}
+inline DbfvCiphertext dbfv_neg(const DbfvCiphertext& ct) {
+    const DbfvParams& dp = *ct.params;
+    const size_t d = ct.num_limbs(), polys = detail::dbfv_polys(ct);
+    auto f = detail::flatten(ct.limbs, polys);
+    std::vector<uint64_t> out(f.size());
+    detail::check(exacto_dbfv_neg(dp.bfv_params->ctx(), f.data(), d, polys, out.data(), 1));
+    return detail::make_dbfv(out, d, polys, ct.degree, ct.mul_depth, ct.params);
+}
+
+// dbfv_relinearize (src/dbfv/keyswitch.rs:9-23)
+inline DbfvCiphertext dbfv_relinearize(const DbfvCiphertext& ct, const RelinKey& rlk) {
+    const DbfvParams& dp = *ct.params;
+    const size_t d = ct.num_limbs(), polys = detail::dbfv_polys(ct), outp = polys < 3 ? polys : 2;
+    if (polys == 3) detail::load_key(rlk);
+    auto f = detail::flatten(ct.limbs, polys);
+    std::vector<uint64_t> out(d * outp * detail::limb_words(dp));
+    detail::check(exacto_dbfv_relinearize(dp.bfv_params->ctx(), f.data(), d, polys, out.data(), 1));
+    return detail::make_dbfv(out, d, outp, ct.degree, ct.mul_depth, ct.params);
+}
+
+// dbfv_apply_automorphism (src/dbfv/advanced.rs:15-29)
+inline DbfvCiphertext dbfv_apply_automorphism(const DbfvCiphertext& ct, const GaloisKey& gk) {
+    const DbfvParams& dp = *ct.params;
+    const size_t d = ct.num_limbs(), polys = detail::dbfv_polys(ct);
+    if (polys != 2) throw ExactoError(1, "invalid parameter: automorphism requires degree-1 ciphertext");
+    auto f = detail::flatten(ct.limbs, polys);
+    std::vector<uint64_t> key;
+    for (auto& k : gk.keys) {
+        key.insert(key.end(), k.first.data.begin(), k.first.data.end());
+        key.insert(key.end(), k.second.data.begin(), k.second.data.end());
+    }
+    std::vector<uint64_t> out(f.size());
+    detail::check(exacto_dbfv_apply_automorphism(dp.bfv_params->ctx(), f.data(), d, polys, gk.element,
+                                                 key.empty() ? nullptr : key.data(), gk.keys.size(), out.data(), 1));
+    return detail::make_dbfv(out, d, 2, ct.degree, ct.mul_depth, ct.params);
+}
+
+// dbfv_div_by_base (src/dbfv/advanced.rs:36-93): the result carries new DbfvParams with p / base.
+inline DbfvCiphertext dbfv_div_by_base(const DbfvCiphertext& ct) {
+    const DbfvParams& dp = *ct.params;
+    auto f = detail::flatten_dbfv(ct);
+    std::vector<uint64_t> out(f.size());
+    uint64_t new_plain = 0;
+    detail::check(exacto_dbfv_div_by_base(dp.bfv_params->ctx(), dp.num_digits, dp.base, dp.plain_modulus, f.data(),
+                                          out.data(), 1, &new_plain));
+    auto np = std::make_shared<DbfvParams>(DbfvParams{dp.bfv_params, dp.base, dp.num_digits, new_plain});
+    const size_t degree = std::max<size_t>(ct.degree ? ct.degree - 1 : 0, 1);  // saturating_sub(1).max(1)
+    return detail::make_dbfv(out, dp.num_digits, 2, degree, ct.mul_depth, np);
+}
+
+// dbfv_change_base (src/dbfv/advanced.rs:99-160): new DbfvParams (new_base, new_num_digits, p).
+inline DbfvCiphertext dbfv_change_base(const DbfvCiphertext& ct, uint64_t new_base, size_t new_num_digits) {
+    const DbfvParams& dp = *ct.params;
+    auto f = detail::flatten_dbfv(ct);
+    std::vector<uint64_t> out(std::max<size_t>(new_num_digits, 1) * 2 * detail::limb_words(dp));
+    detail::check(exacto_dbfv_change_base(dp.bfv_params->ctx(), dp.num_digits, dp.base, dp.plain_modulus, new_base,
+                                          new_num_digits, f.data(), out.data(), 1));
+    auto np = std::make_shared<DbfvParams>(DbfvParams{dp.bfv_params, new_base, new_num_digits, dp.plain_modulus});
+    return detail::make_dbfv(out, new_num_digits, 2, new_num_digits, ct.mul_depth, np);
+}
+
 // The benchmark chain of src/bin/paper_repro.rs:203-236: x * y^depth with mul_depth reset before
 // every dbfv_mul (guard bypass), run device-resident in one call.
 inline DbfvCiphertext dbfv_mul_chain(const DbfvCiphertext& x, const DbfvCiphertext& y, const RelinKey& rlk,

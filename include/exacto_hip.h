@@ -249,6 +249,113 @@ int exacto_dbfv_decrypt_poly(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t 
 int exacto_dbfv_decrypt_poly_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
                                  const uint64_t* ct, const uint64_t* sk, uint64_t* out, size_t batch);
 
+/* ---- dBFV beyond the product: encryption, limb-wise operations, maps between digit vectors ----
+ * All on the dBFV layout [B][d][polys][L][n].  DbfvCiphertext.degree is not carried over this
+ * ABI; a binding keeps it (INTEGRATION.md gives the rule of each function).  Depth arrays as in
+ * exacto_dbfv_mul: host uint32_t[B], NULL = 0, depth_out may be NULL. */
+
+/* dbfv_encrypt_sk_with_rng / dbfv_encrypt_with_rng (dbfv/encrypt.rs:27-35, 73-81, 105-118):
+ * values [B] scalars (DEVICE pointer for _dev), each reduced mod p (taken as is for p = 2^64),
+ * decomposed into d base-b digits (decomposition.rs:8-16, excess digits dropped); limb k of item b
+ * encrypts the constant polynomial of digit k.  ct = [B][d][2][L][n].  sk / pk / sigma / key /
+ * stream as exacto_encrypt_sk / exacto_encrypt_pk, and the randomness is theirs: limb k of item b
+ * is bit for bit item b*d + k of exacto_encrypt_sk/pk called with the same (key, stream, sigma) on
+ * the [B*d][n] digit plaintexts.  Errors: those of DbfvParams::new, then InvalidParam "dBFV base
+ * {b} must be <= BFV plaintext modulus {t}" (encrypt.rs:152-159). */
+int exacto_dbfv_encrypt_sk(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                           const uint64_t* values, const uint64_t* sk, double sigma, const uint64_t* key,
+                           uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_dbfv_encrypt_sk_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                               const uint64_t* values, const uint64_t* sk, double sigma, const uint64_t* key,
+                               uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_dbfv_encrypt_pk(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                           const uint64_t* values, const uint64_t* pk, double sigma, const uint64_t* key,
+                           uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_dbfv_encrypt_pk_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                               const uint64_t* values, const uint64_t* pk, double sigma, const uint64_t* key,
+                               uint64_t stream, uint64_t* ct, size_t batch);
+/* dbfv_encrypt_poly_sk_with_rng / dbfv_encrypt_poly_with_rng (dbfv/encrypt.rs:51-60, 94-103,
+ * 120-141): pt [B][n] coefficients, each reduced mod p; limb k encrypts the polynomial of the k-th
+ * digits.  p = 2^64 is InvalidParam "polynomial dBFV plaintext requires finite plain_modulus
+ * (plain_modulus=0 is scalar-only)". */
+int exacto_dbfv_encrypt_poly_sk(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                const uint64_t* pt, const uint64_t* sk, double sigma, const uint64_t* key,
+                                uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_dbfv_encrypt_poly_sk_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                    const uint64_t* pt, const uint64_t* sk, double sigma, const uint64_t* key,
+                                    uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_dbfv_encrypt_poly_pk(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                const uint64_t* pt, const uint64_t* pk, double sigma, const uint64_t* key,
+                                uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_dbfv_encrypt_poly_pk_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                    const uint64_t* pt, const uint64_t* pk, double sigma, const uint64_t* key,
+                                    uint64_t stream, uint64_t* ct, size_t batch);
+
+/* dbfv_add / dbfv_sub (dbfv/eval.rs:11-58): a = [B][d1][polys1][L][n], b = [B][d2][polys2][L][n] ->
+ * out = [B][d1][max(polys1, polys2)][L][n], every limb by the rule of exacto_bfv_add / exacto_bfv_sub
+ * (aliasing included).  d1 != d2 is DimensionMismatch {expected d1, got d2} (eval.rs:15-20);
+ * depth_out = max(depth_a, depth_b).
+ * dbfv_neg (eval.rs:61-71): ct, out = [B][d][polys][L][n].
+ * dbfv_relinearize (dbfv/keyswitch.rs:9-23): exacto_relinearize on every limb with the resident key:
+ * [B][d][3][L][n] -> [B][d][2][L][n]; polys < 3 cloned; polys > 3 the reference's error.
+ * dbfv_apply_automorphism (dbfv/advanced.rs:15-29): exacto_bfv_apply_automorphism on every limb. */
+int exacto_dbfv_add(exacto_ctx* ctx, const uint64_t* a, size_t d1, size_t polys1, const uint64_t* b, size_t d2,
+                    size_t polys2, uint64_t* out, size_t batch, const uint32_t* depth_a, const uint32_t* depth_b,
+                    uint32_t* depth_out);
+int exacto_dbfv_add_dev(exacto_ctx* ctx, const uint64_t* a, size_t d1, size_t polys1, const uint64_t* b, size_t d2,
+                        size_t polys2, uint64_t* out, size_t batch, const uint32_t* depth_a,
+                        const uint32_t* depth_b, uint32_t* depth_out);
+int exacto_dbfv_sub(exacto_ctx* ctx, const uint64_t* a, size_t d1, size_t polys1, const uint64_t* b, size_t d2,
+                    size_t polys2, uint64_t* out, size_t batch, const uint32_t* depth_a, const uint32_t* depth_b,
+                    uint32_t* depth_out);
+int exacto_dbfv_sub_dev(exacto_ctx* ctx, const uint64_t* a, size_t d1, size_t polys1, const uint64_t* b, size_t d2,
+                        size_t polys2, uint64_t* out, size_t batch, const uint32_t* depth_a,
+                        const uint32_t* depth_b, uint32_t* depth_out);
+int exacto_dbfv_neg(exacto_ctx* ctx, const uint64_t* ct, size_t d, size_t polys, uint64_t* out, size_t batch);
+int exacto_dbfv_neg_dev(exacto_ctx* ctx, const uint64_t* ct, size_t d, size_t polys, uint64_t* out, size_t batch);
+int exacto_dbfv_relinearize(exacto_ctx* ctx, const uint64_t* ct, size_t d, size_t polys, uint64_t* out,
+                            size_t batch);
+int exacto_dbfv_relinearize_dev(exacto_ctx* ctx, const uint64_t* ct, size_t d, size_t polys, uint64_t* out,
+                                size_t batch);
+int exacto_dbfv_apply_automorphism(exacto_ctx* ctx, const uint64_t* ct, size_t d, size_t polys, uint64_t element,
+                                   const uint64_t* gk, size_t num_keys, uint64_t* out, size_t batch);
+int exacto_dbfv_apply_automorphism_dev(exacto_ctx* ctx, const uint64_t* ct, size_t d, size_t polys,
+                                       uint64_t element, const uint64_t* gk, size_t num_keys, uint64_t* out,
+                                       size_t batch);
+
+/* Linear maps between digit vectors, the common core of dbfv_div_by_base and dbfv_change_base
+ * (dbfv/advanced.rs:36-160): out[b][j] = sum_i s_ji * in[b][i] per component, limb and slot, with
+ * s_ji = (matrix[j][i] mod t) mod q_l: the reference's bfv_scalar_plain_mul (advanced.rs:162-171)
+ * followed by bfv_add, in canonical residues.  matrix = [d_out][d_in] HOST u64 (also for _dev);
+ * in = [B][d_in][polys][L][n], out = [B][d_out][polys][L][n]; a row of zeros gives the zero
+ * ciphertext (the reference's bfv_sub(x, x)).  One kernel launch, no intermediate ciphertexts.
+ * out must not overlap in, and _dev buffers are 16-byte aligned (InvalidParam otherwise).  A call
+ * with the matrix of the previous call reuses the resident scalar table and stays asynchronous; a
+ * new matrix waits for the context's stream once before it is uploaded. */
+int exacto_dbfv_linear_map(exacto_ctx* ctx, size_t d_in, size_t d_out, size_t polys, const uint64_t* matrix,
+                           const uint64_t* in, uint64_t* out, size_t batch);
+int exacto_dbfv_linear_map_dev(exacto_ctx* ctx, size_t d_in, size_t d_out, size_t polys, const uint64_t* matrix,
+                               const uint64_t* in, uint64_t* out, size_t batch);
+/* dbfv_change_base (advanced.rs:99-160): in = [B][d][2][L][n] -> out = [B][new_d][2][L][n] in base
+ * new_base.  exacto_dbfv_change_base_matrix is the transform alone (advanced.rs:119-130), pure host
+ * code: out[j][i] = digit j of (base^i mod p) in base new_base, out = [new_d][d].  Errors (both):
+ * those of DbfvParams::new(base, d, plain), "new base must be >= 2", "new_num_digits must be >= 1",
+ * then those of DbfvParams::new(new_base, new_d, plain). */
+int exacto_dbfv_change_base_matrix(size_t d, uint64_t base, uint64_t dbfv_plain_modulus, uint64_t new_base,
+                                   size_t new_d, uint64_t* out);
+int exacto_dbfv_change_base(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                            uint64_t new_base, size_t new_d, const uint64_t* in, uint64_t* out, size_t batch);
+int exacto_dbfv_change_base_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                uint64_t new_base, size_t new_d, const uint64_t* in, uint64_t* out, size_t batch);
+/* dbfv_div_by_base (advanced.rs:36-93): in, out = [B][d][2][L][n]; limb 0 = base^-1 (mod t) * in_0 +
+ * in_1, limb i = in_{i+1}, last limb zero; *new_plain = p / base (new_plain may be NULL).  Errors:
+ * "base not invertible modulo BFV plaintext modulus", "plaintext modulus {p} is not divisible by
+ * base {b}" (p printed as 18446744073709551616 for 2^64). */
+int exacto_dbfv_div_by_base(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                            const uint64_t* in, uint64_t* out, size_t batch, uint64_t* new_plain);
+int exacto_dbfv_div_by_base_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                const uint64_t* in, uint64_t* out, size_t batch, uint64_t* new_plain);
+
 /* ---- diagnostics ---- */
 /* Copies the last error message of this thread (NUL-terminated); returns its length. */
 /* ---- key generation and encryption on the device ----
