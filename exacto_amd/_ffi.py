@@ -95,6 +95,10 @@ _SIGS = [
     ("exacto_dbfv_decrypt_poly", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
     ("exacto_dbfv_decrypt_poly_dev", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
     ("exacto_dbfv_mul_chain_dev", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ, _SZ], C.c_int),
+    ("exacto_bfv_noise", [_P, _P, _SZ, _P, _P, _P, _P, _SZ], C.c_int),
+    ("exacto_bfv_noise_dev", [_P, _P, _SZ, _P, _P, _P, _P, _SZ], C.c_int),
+    ("exacto_dbfv_noise", [_P, _SZ, _P, _P, _P, _SZ], C.c_int),
+    ("exacto_dbfv_noise_dev", [_P, _SZ, _P, _P, _P, _SZ], C.c_int),
     *[(f"exacto_dbfv_encrypt_{kind}{sfx}", [_P, _SZ, _U64, _U64, _P, _P, C.c_double, _P, _U64, _P, _SZ], C.c_int)
       for kind in ("sk", "pk", "poly_sk", "poly_pk") for sfx in ("", "_dev")],
     *[(f"exacto_dbfv_{op}{sfx}", [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _SZ, _P, _P, _P], C.c_int)
@@ -287,6 +291,20 @@ def dbfv_change_base_matrix(d: int, base: int, plain: int, new_base: int, new_d:
     out = np.zeros((max(new_d, 1), max(d, 1)), dtype=np.uint64)
     check(load().exacto_dbfv_change_base_matrix(d, base, plain, new_base, new_d, out.ctypes.data))
     return out[:new_d, :d]
+
+
+def noise_budget_bits(noise: int, moduli, plain: int) -> int:
+    """Bits left before the noise reaches floor(Delta / 2), Delta = floor(Q / p): max(0, bitlen(floor(Delta / 2))
+    - bitlen(noise)), an exact integer."""
+    Q = 1
+    for q in moduli:
+        Q *= int(q)
+    return max(0, ((Q // int(plain)) // 2).bit_length() - int(noise).bit_length())
+
+
+def _words_to_ints(words: np.ndarray) -> list[int]:
+    """[B][L] little-endian 64-bit words -> B Python ints."""
+    return [sum(int(w) << (64 * k) for k, w in enumerate(row)) for row in words]
 
 
 def _ptr(a) -> int | None:
@@ -496,6 +514,28 @@ class HipContext:
         check(self._lib.exacto_dbfv_decrypt_poly(self._h, d, base, plain, ct.ctypes.data, sk.ctypes.data,
                                                  out.ctypes.data, ct.shape[0]))
         return out
+
+    def bfv_noise(self, ct: np.ndarray, sk: np.ndarray, expected=None, return_plain: bool = False):
+        """paper_repro.rs:249-281 bfv_noise_inf, exact over the full Q, batched: ct [B][polys][L][n] -> B Python
+        ints max |phase - Delta m| (centred mod Q); m is the decrypted coefficient, or expected [B][n] mod p.
+        return_plain: also the decrypted plaintexts [B][n] (bfv_decrypt's), as (noise, plain)."""
+        ct, sk = _u64(ct), _u64(sk)
+        B = ct.shape[0]
+        exp = _u64(expected).reshape(B, self.n) if expected is not None else None
+        plain = np.zeros((B, self.n), dtype=np.uint64) if return_plain else None
+        words = np.zeros((B, self.L), dtype=np.uint64)
+        check(self._lib.exacto_bfv_noise(self._h, ct.ctypes.data, ct.shape[1], sk.ctypes.data, _ptr(exp), _ptr(plain),
+                                         words.ctypes.data, B))
+        noise = _words_to_ints(words)
+        return (noise, plain) if return_plain else noise
+
+    def dbfv_noise(self, d, ct: np.ndarray, sk: np.ndarray) -> list[int]:
+        """paper_repro.rs:238-247 max_limb_noise batched: ct [B][d][2][L][n] -> B Python ints."""
+        ct, sk = _u64(ct), _u64(sk)
+        B = ct.shape[0]
+        words = np.zeros((B, self.L), dtype=np.uint64)
+        check(self._lib.exacto_dbfv_noise(self._h, d, ct.ctypes.data, sk.ctypes.data, words.ctypes.data, B))
+        return _words_to_ints(words)
 
     # ---- dBFV beyond the product (dbfv/encrypt.rs, eval.rs:11-71, keyswitch.rs, advanced.rs)
     @staticmethod
@@ -955,6 +995,14 @@ class HipContext:
 
     def bfv_decrypt_dev(self, ct, polys, sk, out, batch):
         check(self._lib.exacto_bfv_decrypt_dev(self._h, self._p(ct), polys, self._p(sk), self._p(out), batch))
+
+    def bfv_noise_dev(self, ct, polys, sk, noise_out, batch, expected=None, plain_out=None):
+        """noise_out: [batch][L] uint64 words on the device (exacto_bfv_noise_dev)."""
+        check(self._lib.exacto_bfv_noise_dev(self._h, self._p(ct), polys, self._p(sk), self._p(expected),
+                                             self._p(plain_out), self._p(noise_out), batch))
+
+    def dbfv_noise_dev(self, d, ct, sk, noise_out, batch):
+        check(self._lib.exacto_dbfv_noise_dev(self._h, d, self._p(ct), self._p(sk), self._p(noise_out), batch))
 
     def dbfv_decrypt_dev(self, d, base, plain, ct, sk, out, batch, poly=False):
         fn = self._lib.exacto_dbfv_decrypt_poly_dev if poly else self._lib.exacto_dbfv_decrypt_dev

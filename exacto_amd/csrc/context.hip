@@ -2634,6 +2634,74 @@ extern "C" int exacto_dbfv_decrypt_poly(exacto_ctx* c, size_t d, uint64_t base, 
                      });
 }
 
+// ============================================================== noise (paper_repro.rs:238-281)
+
+// The decryption's phase and inverse NTT into dec_buf, then noise.hip: the maximum of the centred
+// residual |x - m Delta| over each group of `group` consecutive ciphertexts, L binary words each.
+// The per-workgroup partial maxima live behind the phase in dec_buf.  Delta's residues are uploaded
+// on the context's first use of them (as for encryption); nothing else waits for the device.
+static int delta_residues(exacto_ctx* c);
+static int noise_batch(exacto_ctx* c, const u64* ct, size_t polys, long ct_stride, const u64* sk, const u64* expected,
+                       u64* plain_out, u64* noise_out, size_t items, size_t group) {
+    if (polys < 1) return invalid_param("ciphertext has no polynomials");
+    if (items == 0) return 0;
+    const int L = c->L, n = c->n;
+    const bool round = !expected || plain_out;
+    if (round && L >= 2 && (c->K < 1 || c->plain >= c->primes[L]))
+        return fail(EXACTO_ERR_NOT_IMPLEMENTED, "not yet implemented: GPU decryption needs plain_modulus below the "
+                                                "first internal auxiliary prime");
+    if (int e = delta_residues(c)) return e;
+    const size_t phase_words = items * L * (size_t)n;
+    size_t cap = c->dec_bytes;
+    if (grow(&c->dec_buf, &cap, (phase_words + items * noise_chunks(n) * L) * sizeof(u64))) return EXACTO_ERR_HIP;
+    c->dec_bytes = cap;
+    launch_phase(ct, (int)polys, ct_stride, sk, c->dec_buf, (int)items, n, L, c->d_primes, c->stream);
+    CHECK_LAUNCH();
+    if (int e = run_ntt(c, contiguous(c->dec_buf, (long)items, L, 0, L, n), (long)items * L, true)) return e;
+    launch_noise(c->dec_buf, expected, plain_out, c->dec_buf + phase_words, noise_out, (long)items, (int)group, n, L,
+                 c->d_crt, c->d_primes, c->d_delta, c->plain, round, c->stream);
+    CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int exacto_bfv_noise_dev(exacto_ctx* c, const uint64_t* ct, size_t polys, const uint64_t* sk,
+                                    const uint64_t* expected, uint64_t* plain_out, uint64_t* noise_out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    return noise_batch(c, ct, polys, (long)polys * c->L * c->n, sk, expected, plain_out, noise_out, B, 1);
+}
+
+extern "C" int exacto_bfv_noise(exacto_ctx* c, const uint64_t* ct, size_t polys, const uint64_t* sk,
+                                const uint64_t* expected, uint64_t* plain_out, uint64_t* noise_out, size_t B) {
+    if (!c) return invalid_param("null context");
+    // one staged output: [the plaintexts, if asked for][the noise words]
+    const size_t pw = plain_out ? B * (size_t)c->n : 0, nw = B * (size_t)c->L;
+    std::vector<u64> host(pw + nw);
+    std::vector<std::pair<const void*, size_t>> ins = {{ct, B * polys * c->L * poly_bytes(c)}, {sk, c->L * poly_bytes(c)}};
+    if (expected) ins.push_back({expected, B * poly_bytes(c)});
+    if (int e = host_call(c, ins, host.size() * sizeof(u64), host.data(), [&](std::vector<u64*>& dv, u64* o) {
+            return exacto_bfv_noise_dev(c, dv[0], polys, dv[1], expected ? dv[2] : nullptr, plain_out ? o : nullptr,
+                                        o + pw, B);
+        }))
+        return e;
+    if (pw) std::memcpy(plain_out, host.data(), pw * sizeof(u64));
+    if (nw) std::memcpy(noise_out, host.data() + pw, nw * sizeof(u64));
+    return 0;
+}
+
+extern "C" int exacto_dbfv_noise_dev(exacto_ctx* c, size_t d, const uint64_t* ct, const uint64_t* sk,
+                                     uint64_t* noise_out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (d < 1) return invalid_param("num_digits must be >= 1");
+    return noise_batch(c, ct, 2, 2L * c->L * c->n, sk, nullptr, nullptr, noise_out, B * d, d);
+}
+
+extern "C" int exacto_dbfv_noise(exacto_ctx* c, size_t d, const uint64_t* ct, const uint64_t* sk, uint64_t* noise_out,
+                                 size_t B) {
+    if (!c) return invalid_param("null context");
+    return host_call(c, {{ct, B * d * 2 * c->L * poly_bytes(c)}, {sk, c->L * poly_bytes(c)}}, B * c->L * sizeof(u64),
+                     noise_out, [&](std::vector<u64*>& dv, u64* o) { return exacto_dbfv_noise_dev(c, d, dv[0], dv[1], o, B); });
+}
+
 // dBFV multiplication chain with the guard-bypass semantics of paper_repro.rs:203-236 (and the
 // chain of bfv_host.rs:258-288 without its bootstrap): acc <- dbfv_mul(acc, y) `depth` times,
 // both mul_depth reset to 0 before every step; intermediates ping-pong between two
@@ -2868,7 +2936,7 @@ extern "C" int exacto_gen_relin_key_dev(exacto_ctx* c, const uint64_t* sk, doubl
     return 0;
 }
 
-// Delta_i = floor(Q / p) mod q_i (encrypt.rs:205-229), device copy in c->d_delta.
+// Delta_i = floor(Q / p) mod q_i (encrypt.rs:205-229), device copy in c->d_delta (with Shoup companions).
 static int delta_residues(exacto_ctx* c) {
     if (c->delta_ok) return 0;
     // Q as little-endian 64-bit words, then floor(Q / p) by long division, then mod each q_i
@@ -2892,13 +2960,15 @@ static int delta_residues(exacto_ctx* c) {
     bool zero = true;
     for (u64 w : D) zero &= (w == 0);
     if (zero) return invalid_param("ciphertext modulus product Q must be >= plaintext modulus p");
-    std::vector<u64> dr(c->L);
+    // [0, L): the residues; [EXACTO_MAX_L, EXACTO_MAX_L + L): their Shoup companions (noise.hip)
+    std::vector<u64> dr(2 * EXACTO_MAX_L, 0);
     for (int i = 0; i < c->L; ++i) {
         u128 r = 0;
         for (size_t w = D.size(); w-- > 0;) r = ((r << 64) | D[w]) % c->primes[i];
         dr[i] = (u64)r;
+        dr[EXACTO_MAX_L + i] = shoup_h((u64)r, c->primes[i]);
     }
-    if (!c->d_delta) HIP_TRY(dev_alloc((void**)&c->d_delta, EXACTO_MAX_L * sizeof(u64)));
+    if (!c->d_delta) HIP_TRY(dev_alloc((void**)&c->d_delta, 2 * EXACTO_MAX_L * sizeof(u64)));
     if (int e_ = upload(c, c->d_delta, dr.data(), dr.size() * sizeof(u64))) return e_;
     c->delta_ok = true;
     return 0;

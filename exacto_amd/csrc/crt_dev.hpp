@@ -20,6 +20,56 @@ __device__ __forceinline__ bool mr_greater(const u64 (&v)[MAXN], const u64* h, i
     return res == 1;
 }
 
+// ---------------------------------------------------------------- mixed radix helpers
+
+// A residue of one prime moved to another: with NEAR (max prime < 2 * min prime) a value
+// below any prime needs one conditional subtraction, otherwise a full reduce64.
+template <bool NEAR>
+__device__ __forceinline__ u64 xfer(u64 v, u64 q, u64 mu) {
+    if (NEAR) return v >= q ? v - q : v;
+    return reduce64(v, q, mu);
+}
+
+// Garner: residues x[i] mod q_i (i < L) -> mixed-radix digits v (x = v0 + v1 q0 + v2 q0 q1 + ...).
+template <bool NEAR>
+__device__ __forceinline__ void garner_q(u64 (&v)[EXACTO_MAX_L], const u64 (&x)[EXACTO_MAX_L], int L,
+                                         const CrtTables* __restrict__ C,
+                                         const PrimeConst* __restrict__ primes) {
+#pragma unroll
+    for (int i = 0; i < EXACTO_MAX_L; ++i) {
+        if (i < L) {
+            const u64 qi = primes[i].q, mui = primes[i].mu64;
+            u64 t = x[i];
+#pragma unroll
+            for (int k = 0; k < EXACTO_MAX_L; ++k) {
+                if (k < i) {
+                    t = sub_mod(t, xfer<NEAR>(v[k], qi, mui), qi);
+                    t = shoup_mul_red(t, C->gq_w[i][k], C->gq_ws[i][k], qi);
+                }
+            }
+            v[i] = t;
+        }
+    }
+}
+
+
+// sum_k (v_k mod prime_t) * pref[k][t]  -  neg * pref[cnt][t]   (mod prime_t)
+template <int MAXN, int STRIDE, bool NEAR>
+__device__ __forceinline__ u64 mr_eval(const u64 (&v)[MAXN], int cnt, bool neg, const u64* pw,
+                                       const u64* pws, int t, const PrimeConst& P) {
+    const u64 q = P.q, mu = P.mu64;
+    u64 acc = 0;
+#pragma unroll
+    for (int k = 0; k < MAXN; ++k) {
+        if (k < cnt) {
+            const u64 vk = xfer<NEAR>(v[k], q, mu);
+            acc = add_mod(acc, shoup_mul_red(vk, pw[k * STRIDE + t], pws[k * STRIDE + t], q), q);
+        }
+    }
+    if (neg) acc = sub_mod(acc, pw[cnt * STRIDE + t], q);
+    return acc;
+}
+
 // Garner over Q; x[i] < 2 q_i.
 template <int LT>
 __device__ __forceinline__ void garner_q_fast(u64 (&v)[EXACTO_MAX_L], const u64 (&x)[EXACTO_MAX_L], int L_arg,

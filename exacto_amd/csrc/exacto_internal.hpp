@@ -188,6 +188,15 @@ void launch_phase(const u64* ct, int polys, long ct_stride, const u64* sk, u64* 
                   const PrimeConst* primes, hipStream_t s);
 void launch_decrypt_round(const u64* X, u64* out, int items, int n, int L, const CrtTables* ct,
                           const PrimeConst* primes, u64 plain, hipStream_t s);
+// Noise (paper_repro.rs:238-281), noise.hip: X [items][L][n] (the decryption's phase, coefficient domain) ->
+// out [items / group][L] little-endian words of max |x - m Delta| centred mod Q over each group of items;
+// expected / plain_out [items][n] or null; part: workspace of items * noise_chunks(n) * L words;
+// round: compute the decrypted coefficient (L >= 2: needs plain < primes[L]); delta: Delta mod q_i and, EXACTO_MAX_L words on,
+// the Shoup companions
+int noise_chunks(int n);
+void launch_noise(const u64* X, const u64* expected, u64* plain_out, u64* part, u64* out, long items, int group,
+                  int n, int L, const CrtTables* ct, const PrimeConst* primes, const u64* delta, u64 plain,
+                  bool round, hipStream_t s);
 void launch_dbfv_recompose(const u64* digits, u64* out, int items, int n, int d, u64 base, u64 plain, u64 t,
                            bool scalar, hipStream_t s);
 // rows = polynomials of coefQ ([rows][L][n] -> extP [rows][K][n])

@@ -743,6 +743,91 @@ inline CoeffPoly dbfv_decrypt_poly(const DbfvCiphertext& ct, const SecretKey& sk
     return res;
 }
 
+// ---- noise (src/bin/paper_repro.rs:238-281: max_limb_noise, bfv_noise_inf), exact over the full Q
+// A noise value: little-endian 64-bit words, one per ciphertext prime (Q < 2^(64 L)).
+struct Noise {
+    std::vector<uint64_t> words;
+    size_t bit_length() const {
+        for (size_t k = words.size(); k-- > 0;)
+            if (words[k]) return 64 * k + (64 - (size_t)__builtin_clzll(words[k]));
+        return 0;
+    }
+    bool fits_u64() const { return bit_length() <= 64; }
+    // the reference's u64 (paper_repro.rs returns one); throws when the value needs more words
+    uint64_t to_u64() const {
+        if (!fits_u64()) throw ExactoError(1, "invalid parameter: noise value does not fit 64 bits");
+        return words.empty() ? 0 : words[0];
+    }
+};
+
+namespace detail {
+// bitlen(floor(floor(Q / p) / 2)) for Q = prod moduli (host only)
+inline size_t half_delta_bits(const std::vector<uint64_t>& moduli, uint64_t plain) {
+    if (plain == 0) throw ExactoError(1, "invalid parameter: plain_modulus must be non-zero");
+    std::vector<uint64_t> q(1, 1);
+    for (uint64_t m : moduli) {
+        unsigned __int128 carry = 0;
+        for (auto& w : q) {
+            const unsigned __int128 t = (unsigned __int128)w * m + carry;
+            w = (uint64_t)t;
+            carry = t >> 64;
+        }
+        if (carry) q.push_back((uint64_t)carry);
+    }
+    Noise delta;
+    delta.words.resize(q.size());
+    unsigned __int128 rem = 0;
+    for (size_t k = q.size(); k-- > 0;) {
+        const unsigned __int128 cur = (rem << 64) | q[k];
+        delta.words[k] = (uint64_t)(cur / plain);
+        rem = cur % plain;
+    }
+    const size_t bits = delta.bit_length();
+    return bits ? bits - 1 : 0;
+}
+}  // namespace detail
+
+// max(0, bitlen(floor(Delta / 2)) - bitlen(noise)), Delta = floor(Q / p): the bits left before
+// decryption can fail.
+inline size_t noise_budget_bits(const Noise& noise, const std::vector<uint64_t>& moduli, uint64_t plain) {
+    const size_t have = detail::half_delta_bits(moduli, plain), used = noise.bit_length();
+    return have > used ? have - used : 0;
+}
+inline size_t noise_budget_bits(const Noise& noise, const BfvParams& prm) {
+    return noise_budget_bits(noise, prm.ct_moduli, prm.plain_modulus);
+}
+
+// bfv_noise_inf (paper_repro.rs:249-281), batched over ciphertexts of one degree: max |phase - Delta m|
+// centred mod Q against the decrypted m.  At L = 1 the reference's value; for L >= 2 the same formula
+// over the full Q.
+inline std::vector<Noise> bfv_noise_inf(const std::vector<BfvCiphertext>& cts, const SecretKey& sk) {
+    if (cts.empty()) return {};
+    const BfvParams& prm = *cts[0].params;
+    const size_t polys = cts[0].c.size(), L = prm.num_limbs();
+    auto flat = detail::flatten(cts, polys);
+    std::vector<uint64_t> out(cts.size() * L);
+    detail::check(exacto_bfv_noise(prm.ctx(), flat.data(), polys, sk.poly.data.data(), nullptr, nullptr, out.data(),
+                                   cts.size()));
+    std::vector<Noise> res(cts.size());
+    for (size_t b = 0; b < cts.size(); ++b)
+        res[b].words.assign(out.begin() + (long)(b * L), out.begin() + (long)((b + 1) * L));
+    return res;
+}
+inline Noise bfv_noise_inf(const BfvCiphertext& ct, const SecretKey& sk) {
+    return bfv_noise_inf(std::vector<BfvCiphertext>{ct}, sk)[0];
+}
+
+// max_limb_noise (paper_repro.rs:238-247): the maximum of bfv_noise_inf over the limbs.
+inline Noise max_limb_noise(const DbfvCiphertext& ct, const SecretKey& sk) {
+    const auto& dp = *ct.params;
+    auto flat = detail::flatten_dbfv(ct);
+    Noise res;
+    res.words.resize(dp.bfv_params->num_limbs());
+    detail::check(exacto_dbfv_noise(dp.bfv_params->ctx(), dp.num_digits, flat.data(), sk.poly.data.data(),
+                                    res.words.data(), 1));
+    return res;
+}
+
 // ---- exacto::dbfv beyond the product: keygen, encrypt, eval, keyswitch, advanced
 using DbfvParamsPtr = std::shared_ptr<const DbfvParams>;
 

@@ -249,6 +249,33 @@ int exacto_dbfv_decrypt_poly(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t 
 int exacto_dbfv_decrypt_poly_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
                                  const uint64_t* ct, const uint64_t* sk, uint64_t* out, size_t batch);
 
+/* ---- noise measurement (paper_repro.rs:238-281 bfv_noise_inf, max_limb_noise) ----
+ * With Q = prod q_i, p the context's plain modulus, Delta = floor(Q / p) and x_j in [0, Q) the phase
+ * exacto_bfv_decrypt rounds:  e_j = (x_j - m_j Delta) mod Q,  noise = max_j min(e_j, Q - e_j),
+ * where m_j is the decrypted coefficient (expected == NULL) or expected[j] mod p.  Noise against the
+ * decrypted value never exceeds about Delta / 2 + p; to see it past the point where decryption
+ * fails, say in `expected` what the plaintext should be.
+ * At L = 1 this is bfv_noise_inf literally.  For L >= 2 it is the same formula over the full Q (the
+ * extension semantics of the multi-prime configurations; the reference looks at moduli[0] only).
+ * The result is exact: noise_out = [B][L] little-endian 64-bit words (Q < 2^(64 L)), the same from
+ * run to run.  ct = [B][polys][L][n], sk = [L][n] (NTT domain), expected = [B][n] or NULL,
+ * plain_out = [B][n] or NULL: the decrypted m of exacto_bfv_decrypt, a free by-product.
+ * polys < 1 -> InvalidParam as exacto_bfv_decrypt; batch = 0 returns 0.  L >= 2 with p not below the
+ * first internal auxiliary prime is NotImplemented only when the rounding is computed (expected ==
+ * NULL or plain_out != NULL).  The _dev form enqueues on the context's stream and does not wait (but
+ * for the upload of Delta's residues on a context's first use of them, as in exacto_encrypt_sk_dev). */
+int exacto_bfv_noise(exacto_ctx* ctx, const uint64_t* ct, size_t polys, const uint64_t* sk,
+                     const uint64_t* expected, uint64_t* plain_out, uint64_t* noise_out, size_t batch);
+int exacto_bfv_noise_dev(exacto_ctx* ctx, const uint64_t* ct, size_t polys, const uint64_t* sk,
+                         const uint64_t* expected, uint64_t* plain_out, uint64_t* noise_out, size_t batch);
+/* max_limb_noise: the maximum over the d limbs of each dBFV ciphertext, against each limb's decrypted
+ * value.  ct = [B][d][2][L][n], noise_out = [B][L].  The per-limb values are exacto_bfv_noise with
+ * polys = 2 and batch B * d on the same memory.  d = 0 -> InvalidParam as exacto_dbfv_decrypt. */
+int exacto_dbfv_noise(exacto_ctx* ctx, size_t d, const uint64_t* ct, const uint64_t* sk, uint64_t* noise_out,
+                      size_t batch);
+int exacto_dbfv_noise_dev(exacto_ctx* ctx, size_t d, const uint64_t* ct, const uint64_t* sk, uint64_t* noise_out,
+                          size_t batch);
+
 /* ---- dBFV beyond the product: encryption, limb-wise operations, maps between digit vectors ----
  * All on the dBFV layout [B][d][polys][L][n].  DbfvCiphertext.degree is not carried over this
  * ABI; a binding keeps it (INTEGRATION.md gives the rule of each function).  Depth arrays as in
