@@ -88,6 +88,10 @@ _SIGS = [
     ("exacto_dbfv_mul_chain", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ, _SZ], C.c_int),
     ("exacto_dbfv_mul_limbs", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ, _P, _SZ], C.c_int),
     ("exacto_dbfv_mul_limbs_dev", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ, _P, _SZ], C.c_int),
+    ("exacto_bfv_mul_sum", [_P, _P, _SZ, _P, _SZ, _P, _P, _P, _SZ, _SZ, _P, _SZ], C.c_int),
+    ("exacto_bfv_mul_sum_dev", [_P, _P, _SZ, _P, _SZ, _P, _P, _P, _SZ, _SZ, _P, _SZ], C.c_int),
+    ("exacto_ctx_set_mul_sum_group", [_P, _SZ], C.c_int),
+    ("exacto_bfv_mul_sum_info", [_P, C.POINTER(_SZ), C.POINTER(C.c_int)], C.c_int),
     ("exacto_bfv_decrypt", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_decrypt_dev", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
     ("exacto_dbfv_decrypt", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
@@ -971,6 +975,56 @@ class HipContext:
         ls = np.ascontiguousarray(np.asarray(limbs, dtype=np.uint32))
         check(self._lib.exacto_dbfv_mul_limbs_dev(self._h, d, base, plain, self._p(a), self._p(b), self._p(out),
                                                   batch, ls.ctypes.data if ls.size else None, ls.size))
+
+    # ---- sums of ciphertext products (exacto_bfv_mul_sum)
+    @staticmethod
+    def _mul_sum_terms(terms, nslots):
+        """terms: [(ia, ib, slot)] -> three uint32 arrays; malformed lists are rejected here, before any
+        library call (the library checks the indices against na / nb)."""
+        terms = list(terms)
+        ia, ib, sl = [], [], []
+        for k, t in enumerate(terms):
+            try:
+                x, y, s = t
+            except (TypeError, ValueError):
+                raise ValueError(f"bfv_mul_sum: term {k} is not an (ia, ib, slot) triple: {t!r}") from None
+            for name, v in (("ia", x), ("ib", y), ("slot", s)):
+                if int(v) != v or not 0 <= int(v) < 1 << 32:
+                    raise ValueError(f"bfv_mul_sum: term {k} has {name} = {v!r} (need an index in [0, 2^32))")
+            if int(s) >= nslots:
+                raise ValueError(f"bfv_mul_sum: term {k} has slot {int(s)} >= nslots = {nslots}")
+            ia.append(int(x)); ib.append(int(y)); sl.append(int(s))
+        if int(nslots) != nslots or nslots < 0:
+            raise ValueError(f"bfv_mul_sum: nslots = {nslots!r}")
+        return tuple(np.array(v, dtype=np.uint32) for v in (ia, ib, sl))
+
+    def bfv_mul_sum(self, a: np.ndarray, b: np.ndarray, terms, nslots: int) -> np.ndarray:
+        """out[i][s] = sum over terms (ia, ib, s) of bfv_mul_and_relin(a[i][ia], b[i][ib]), one key switch
+        per sum: a [B][na][2][L][n], b [B][nb][2][L][n] -> [B][nslots][2][L][n]."""
+        ia, ib, sl = self._mul_sum_terms(terms, nslots)
+        a, b = _u64(a), _u64(b)
+        B = a.shape[0]
+        out = np.zeros((B, nslots, 2, self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_bfv_mul_sum(self._h, a.ctypes.data, a.shape[1], b.ctypes.data, b.shape[1],
+                                           _ptr(ia), _ptr(ib), _ptr(sl), ia.size, nslots, out.ctypes.data, B))
+        return out
+
+    def bfv_mul_sum_dev(self, a, na, b, nb, terms, nslots, out, batch):
+        """Device buffers a [B][na][2][L][n], b [B][nb][2][L][n] (may be the same), out [B][nslots][2][L][n];
+        terms on the host.  Asynchronous on the context's stream."""
+        ia, ib, sl = self._mul_sum_terms(terms, nslots)
+        check(self._lib.exacto_bfv_mul_sum_dev(self._h, self._p(a), na, self._p(b), nb, _ptr(ia), _ptr(ib), _ptr(sl),
+                                               ia.size, nslots, self._p(out), batch))
+
+    def set_mul_sum_group(self, max_products: int):
+        """At most this many products of one output key-switched as one sum (0: the context's own limit)."""
+        check(self._lib.exacto_ctx_set_mul_sum_group(self._h, max_products))
+
+    def mul_sum_info(self) -> dict:
+        """{"group_max", "last_mode"} (exacto_bfv_mul_sum_info)."""
+        gm, md = _SZ(0), C.c_int(-1)
+        check(self._lib.exacto_bfv_mul_sum_info(self._h, C.byref(gm), C.byref(md)))
+        return {"group_max": int(gm.value), "last_mode": int(md.value)}
 
     # ---- RCCL collectives (exacto_hip.h; comm = RcclComm)
     def broadcast_relin_key(self, comm: "RcclComm", root: int, num_keys: int):

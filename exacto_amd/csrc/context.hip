@@ -260,6 +260,8 @@ struct exacto_ctx {
     bool ks32_lazy_active = false;
     int ks32_need_m = 1;          // the most key-switch sums per output limb a dbfv_mul of this context asked for
     int last_dbfv_ks = -1;        // exacto_ctx_info.dbfv_key_switch
+    int last_mul_sum_mode = -1;   // exacto_bfv_mul_sum_info: the same codes for the last bfv_mul_sum
+    size_t mul_sum_cap = 0;       // exacto_ctx_set_mul_sum_group (0: the context's own limit)
     // a dBFV pass with shared extensions: d and its products per item (0: plain BFV products), for
     // run_inv_tensor's algorithmic bytes and the tensor kernels' prime-major block order
     int tensor_share_d = 0, tensor_share_npairs = 0;
@@ -377,9 +379,15 @@ struct exacto_ctx {
     size_t io_bytes = 0;
     u64* prod = nullptr;
     size_t prod_bytes = 0;
-    // dBFV plan cache
+    // product-sum plan cache (dbfv_mul's index rule, or bfv_mul_sum's term lists: cached_kind)
     u64* d_off = nullptr;
     size_t off_cap = 0;
+    int cached_kind = -1;            // 0: dbfv_plan, 1: mul_sum_plan; -1: none
+    std::vector<uint32_t> cached_ms; // mul_sum_plan: ia, ib, slot lists, then na, nb, nslots, group limit
+    int cached_ngroups = 0;          // mul_sum_plan: groups of the cached plan (its "output limbs")
+    int* d_slot_start = nullptr;     // ... and, when a slot has several, slot s = groups [start[s], start[s+1])
+    u64* gsum_buf = nullptr;         // bfv_mul_sum: the groups' coefficient-domain results [B][groups][2][L][n]
+    size_t gsum_cap = 0;
     size_t cached_B = 0, cached_d = 0;
     u64 cached_base = 0, cached_p = 0;
     int cached_npairs = 0;
@@ -1165,6 +1173,7 @@ extern "C" void exacto_ctx_destroy(exacto_ctx* c) {
     }
     if (c->ev_twin_in) (void)hipEventDestroy(c->ev_twin_in);
     free_dev(c->io); free_dev(c->prod); free_dev(c->d_off); free_dev(c->d_term_start); free_dev(c->d_terms);
+    free_dev(c->d_slot_start); free_dev(c->gsum_buf);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     free_dev(c->boot_buf); free_dev(c->boot_slots);
     delete c;
@@ -1255,7 +1264,7 @@ extern "C" int exacto_ctx_load_relin_key(exacto_ctx* c, const uint64_t* rlk, siz
 enum ProfKind : int {
     PK_FWD = 0, PK_INV = 1, PK_TENSOR = 2, PK_POLYMUL = 3, PK_LIFT = 4, PK_SCALE = 5, PK_KS_DIGITS = 6,
     PK_KS_MAC = 7, PK_KS_CRT = 8, PK_PAIRSUM = 9, PK_PSUM_SCALE = 10, PK_TENSOR_C2 = 11, PK_DIGIT_SUM = 12,
-    PK_COMBINE = 13, PK_HPS_EXT = 14, PK_RELIN_MAC = 15, PK_HPS_SCALE = 16, PK_COUNT = 17
+    PK_COMBINE = 13, PK_HPS_EXT = 14, PK_RELIN_MAC = 15, PK_HPS_SCALE = 16, PK_GROUP_SUM = 17, PK_COUNT = 18
 };
 
 struct ProfScope {
@@ -2098,14 +2107,58 @@ static std::vector<std::vector<i64>> small_reps(u64 base, size_t d, u64 p) {
     return reps;
 }
 
+// Uploads a product-sum plan: `pairs` = the (left, right) operand indices of the npairs products of one
+// item (left in [0, na), right in [0, nb)), and for each of the dout outputs the products it sums
+// (terms [start[s], start[s + 1]), CombineTerm::pair indexing `pairs`).  dbfv_mul's index rule
+// (dbfv_plan) and bfv_mul_sum's term lists (mul_sum_plan) are its two producers; the caller sets the
+// cache key.  d_off: [0, BP): a offsets, [BP, 2BP): b offsets (ciphertexts), [2BP, 4BP): the same
+// into the per-ciphertext extension buffers (ext_a = [B na], ext_b = [B nb] ciphertexts).
+static int plan_upload(exacto_ctx* c, size_t B, size_t na, size_t nb, const std::vector<std::pair<int, int>>& pairs,
+                       const std::vector<int>& start, const std::vector<CombineTerm>& terms) {
+    c->cached_kind = -1;   // (a failed upload leaves no plan)
+    const int npairs = (int)pairs.size();
+    const size_t dout = start.size() - 1;
+    // ks32 sums before the lift: every combine term a plain sum (zero reps), at most this many per limb
+    int sum_m = 0;
+    for (const CombineTerm& t : terms) if (t.coef != 1) sum_m = -1;
+    for (size_t so = 0; so < dout && sum_m >= 0; ++so) sum_m = std::max(sum_m, start[so + 1] - start[so]);
+    const long Ln2 = 2L * c->L * c->n, Kn2 = 2L * c->K * c->n;
+    const size_t BP = B * npairs;
+    std::vector<u64> off(4 * BP);
+    for (size_t b = 0; b < B; ++b)
+        for (int pi = 0; pi < npairs; ++pi) {
+            off[b * npairs + pi] = (u64)((b * na + pairs[pi].first) * Ln2);
+            off[BP + b * npairs + pi] = (u64)((b * nb + pairs[pi].second) * Ln2);
+            off[2 * BP + b * npairs + pi] = (u64)((b * na + pairs[pi].first) * Kn2);
+            off[3 * BP + b * npairs + pi] = (u64)((b * nb + pairs[pi].second) * Kn2);
+        }
+    size_t cap = c->off_cap;
+    if (grow(&c->d_off, &cap, off.size() * sizeof(u64) + 8)) return EXACTO_ERR_HIP;
+    c->off_cap = cap;
+    if (int e_ = upload(c, c->d_off, off.data(), off.size() * sizeof(u64))) return e_;
+    free_dev(c->d_term_start);
+    free_dev(c->d_terms);
+    c->d_term_start = nullptr;
+    c->d_terms = nullptr;
+    HIP_TRY(dev_alloc((void**)&c->d_term_start, start.size() * sizeof(int)));
+    if (int e_ = upload(c, c->d_term_start, start.data(), start.size() * sizeof(int))) return e_;
+    HIP_TRY(dev_alloc((void**)&c->d_terms, std::max<size_t>(terms.size(), 1) * sizeof(CombineTerm)));
+    if (!terms.empty())
+        if (int e_ = upload(c, c->d_terms, terms.data(), terms.size() * sizeof(CombineTerm))) return e_;
+    c->cached_B = B;
+    c->cached_npairs = npairs;
+    c->cached_sum_m = sum_m;
+    return 0;
+}
+
 // The product list and combine terms of a dbfv_mul batch (dbfv/eval.rs:109-132 + reduce,
 // reduction.rs:34-52) for the output limbs `limbs` (all of 0..d-1, or the subset one GPU computes
 // when the limbs of one dbfv_mul are split across GPUs): output slot s = limb limbs[s] gets the sum
 // over pairs (i, j) with i + j == limbs[s] plus the reps folding of the high limbs i + j >= d.  Only
 // the pairs some listed limb uses are multiplied.
 static int dbfv_plan(exacto_ctx* c, size_t B, size_t d, u64 base, u64 plain, const std::vector<int>& limbs) {
-    if (c->cached_B == B && c->cached_d == d && c->cached_base == base && c->cached_p == plain && c->d_off &&
-        c->cached_limbs == limbs)
+    if (c->cached_kind == 0 && c->cached_B == B && c->cached_d == d && c->cached_base == base && c->cached_p == plain &&
+        c->d_off && c->cached_limbs == limbs)
         return 0;
     const auto reps = small_reps(base, d, plain);
     const size_t dout = limbs.size();
@@ -2131,37 +2184,55 @@ static int dbfv_plan(exacto_ctx* c, size_t B, size_t d, u64 base, u64 plain, con
         }
     }
     start[dout] = (int)terms.size();
-    // ks32 sums before the lift: every combine term a plain sum (zero reps), at most this many per limb
-    int sum_m = 0;
-    for (const CombineTerm& t : terms) if (t.coef != 1) sum_m = -1;
-    for (size_t so = 0; so < dout && sum_m >= 0; ++so) sum_m = std::max(sum_m, start[so + 1] - start[so]);
-    const long Ln2 = 2L * c->L * c->n, Kn2 = 2L * c->K * c->n;
-    // [0, BP): a offsets, [BP, 2BP): b offsets (ciphertexts), [2BP, 4BP): the same into the
-    // per-ciphertext extension buffers
-    const size_t BP = B * npairs;
-    std::vector<u64> off(4 * BP);
-    for (size_t b = 0; b < B; ++b)
-        for (int pi = 0; pi < npairs; ++pi) {
-            off[b * npairs + pi] = (u64)((b * d + pairs[pi].first) * Ln2);
-            off[BP + b * npairs + pi] = (u64)((b * d + pairs[pi].second) * Ln2);
-            off[2 * BP + b * npairs + pi] = (u64)((b * d + pairs[pi].first) * Kn2);
-            off[3 * BP + b * npairs + pi] = (u64)((b * d + pairs[pi].second) * Kn2);
-        }
-    size_t cap = c->off_cap;
-    if (grow(&c->d_off, &cap, off.size() * sizeof(u64) + 8)) return EXACTO_ERR_HIP;
-    c->off_cap = cap;
-    if (int e_ = upload(c, c->d_off, off.data(), off.size() * sizeof(u64))) return e_;
-    free_dev(c->d_term_start);
-    free_dev(c->d_terms);
-    HIP_TRY(dev_alloc((void**)&c->d_term_start, start.size() * sizeof(int)));
-    if (int e_ = upload(c, c->d_term_start, start.data(), start.size() * sizeof(int))) return e_;
-    HIP_TRY(dev_alloc((void**)&c->d_terms, std::max<size_t>(terms.size(), 1) * sizeof(CombineTerm)));
-    if (!terms.empty())
-        if (int e_ = upload(c, c->d_terms, terms.data(), terms.size() * sizeof(CombineTerm))) return e_;
-    c->cached_B = B; c->cached_d = d; c->cached_base = base; c->cached_p = plain;
-    c->cached_npairs = npairs;
+    if (int e = plan_upload(c, B, d, d, pairs, start, terms)) return e;
+    c->cached_kind = 0;
+    c->cached_d = d; c->cached_base = base; c->cached_p = plain;
     c->cached_limbs = limbs;
-    c->cached_sum_m = sum_m;
+    return 0;
+}
+
+// The plan of a bfv_mul_sum: product t = (ia[t], ib[t]) (a pair listed twice is two products: it counts
+// twice), the terms of each output slot in groups of at most `gcap` products (0: one group per slot),
+// groups ordered by slot.  Each group is one "output limb" of the pass; slot_start (uploaded when a
+// slot has several groups) lists each slot's groups for the group sum.
+static int mul_sum_plan(exacto_ctx* c, size_t B, size_t na, size_t nb, const uint32_t* ia, const uint32_t* ib,
+                        const uint32_t* slot, size_t nterms, size_t nslots, size_t gcap) {
+    std::vector<uint32_t> key;
+    key.reserve(3 * nterms + 4);
+    key.insert(key.end(), ia, ia + nterms);
+    key.insert(key.end(), ib, ib + nterms);
+    key.insert(key.end(), slot, slot + nterms);
+    for (size_t v : {na, nb, nslots, gcap}) key.push_back((uint32_t)std::min<size_t>(v, 0xffffffffu));
+    if (c->cached_kind == 1 && c->cached_B == B && c->d_off && c->cached_ms == key) return 0;
+    std::vector<std::pair<int, int>> pairs(nterms);
+    for (size_t t = 0; t < nterms; ++t) pairs[t] = {(int)ia[t], (int)ib[t]};
+    std::vector<int> start{0}, slot_start{0};
+    std::vector<CombineTerm> terms;
+    for (size_t s = 0; s < nslots; ++s) {
+        size_t in_group = 0;
+        for (size_t t = 0; t < nterms; ++t) {
+            if (slot[t] != s) continue;
+            if (gcap && in_group == gcap) {
+                start.push_back((int)terms.size());
+                in_group = 0;
+            }
+            terms.push_back({(int)t, 0, 1});
+            ++in_group;
+        }
+        start.push_back((int)terms.size());
+        slot_start.push_back((int)start.size() - 1);
+    }
+    if (int e = plan_upload(c, B, na, nb, pairs, start, terms)) return e;
+    const size_t ngroups = start.size() - 1;
+    if (ngroups > nslots) {
+        free_dev(c->d_slot_start);
+        c->d_slot_start = nullptr;
+        HIP_TRY(dev_alloc((void**)&c->d_slot_start, slot_start.size() * sizeof(int)));
+        if (int e_ = upload(c, c->d_slot_start, slot_start.data(), slot_start.size() * sizeof(int))) return e_;
+    }
+    c->cached_kind = 1;
+    c->cached_ms = key;
+    c->cached_ngroups = (int)ngroups;
     return 0;
 }
 
@@ -2216,14 +2287,17 @@ static int extend_cts(exacto_ctx* c, const u64* cts, size_t ncts, u64* ext, cons
     return 0;
 }
 
+// One pass over the resident plan (plan_upload): a = [B][na][2][L][n], b = [B][nb][2][L][n], the plan's
+// dout outputs per item, each the sum of its products, relinearised.
 // b_extended: c->ext_b already holds the extensions of b (a chain's constant right operand)
-// out = [B][dout][2][L][n] for the output limbs `limbs` (dout = limbs.size()), one group of items
-static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* a,
-                          const uint64_t* b, uint64_t* out, size_t B, bool b_extended,
-                          const std::vector<int>* limbs) {
-    const size_t dout = limbs->size();
-    if (int e = dbfv_plan(c, B, d, base, plain, *limbs)) return e;
+// nslots == dout (dbfv_mul: the outputs are the limbs): out = [B][dout][2][L][n].  nslots < dout
+// (bfv_mul_sum with more products per slot than one key switch lifts): the dout outputs are groups,
+// formed in gsum_buf and added per slot (mul_sum_plan's slot_start) before the forward transform of
+// out = [B][nslots][2][L][n].  *mode: the key switch taken, exacto_ctx_info.dbfv_key_switch's codes.
+static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a, const uint64_t* b, uint64_t* out,
+                         size_t B, bool b_extended, size_t dout, size_t nslots, int* mode) {
     const int npairs = c->cached_npairs;
+    const bool grouped = nslots < dout;
     const long Ln2 = 2L * c->L * c->n;
     const long P = (long)B * npairs;
     size_t cap = c->prod_bytes;
@@ -2234,17 +2308,17 @@ static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
     op.a = a; op.a_off = c->d_off; op.a_stride = 0;
     op.b = b; op.b_off = c->d_off + BP; op.b_stride = 0;
     if (c->share_ext && c->K > 0 && !c->deferred_code) {
-        const size_t nct = B * d, bytes = nct * 2 * c->K * poly_bytes(c);
+        const size_t bytes_a = B * na * 2 * c->K * poly_bytes(c), bytes_b = B * nb * 2 * c->K * poly_bytes(c);
         if (c->ext_a_ready) {   // made by the previous chain step (same ciphertexts, same buffer size)
-            if (c->ext_a_cap < bytes) return fail(EXACTO_ERR_HIP, "internal: pre-extended operand buffer too small");
+            if (c->ext_a_cap < bytes_a) return fail(EXACTO_ERR_HIP, "internal: pre-extended operand buffer too small");
         } else {
-            if (grow(&c->ext_a, &c->ext_a_cap, bytes)) return EXACTO_ERR_HIP;
-            if (int e = extend_cts(c, a, nct, c->ext_a, c->coef_in)) return e;
+            if (grow(&c->ext_a, &c->ext_a_cap, bytes_a)) return EXACTO_ERR_HIP;
+            if (int e = extend_cts(c, a, B * na, c->ext_a, c->coef_in)) return e;
         }
         c->ext_a_ready = false;
         if (!b_extended) {
-            if (grow(&c->ext_b, &c->ext_b_cap, bytes)) return EXACTO_ERR_HIP;
-            if (int e = extend_cts(c, b, nct, c->ext_b)) return e;
+            if (grow(&c->ext_b, &c->ext_b_cap, bytes_b)) return EXACTO_ERR_HIP;
+            if (int e = extend_cts(c, b, B * nb, c->ext_b)) return e;
         }
         op.ea = c->ext_a; op.ea_off = c->d_off + 2 * BP;
         op.eb = c->ext_b; op.eb_off = c->d_off + 3 * BP;
@@ -2272,7 +2346,7 @@ static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
     const bool use_prim = on && m <= c->ks32_sum_max;
     const bool use_wide = on && !use_prim && c->kw.S > 0 && m <= c->kw.sum_max;
     const bool sum_ks = use_prim || use_wide;
-    c->last_dbfv_ks = use_prim ? 1 : use_wide ? 2 : 0;
+    *mode = use_prim ? 1 : use_wide ? 2 : 0;
     const int S = use_wide ? c->kw.S : c->S32;
     const Prime32* p32 = use_wide ? c->kw.d_p32 : c->d_p32;
     const Ks32Tables* kst = use_wide ? c->kw.d_kst : c->d_kst;
@@ -2288,6 +2362,11 @@ static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
     const bool hps_sum = c->path == EXACTO_PATH_HPS && c->hps_sum_env && m > 0 && c->gbase <= 65536 &&
                          (u64)m * (c->gbase / 2) <= 32767 && c->rlk_loaded && gu > 0 && c->n >= 1024 &&
                          !c->deferred_code;
+    if (grouped) {
+        // (the HPS sum multiplies with the key after the forward transform, once per output: never grouped)
+        if (hps_sum) return fail(EXACTO_ERR_HIP, "internal: grouped product sums on the HPS digit-sum path");
+        if (grow(&c->gsum_buf, &c->gsum_cap, B * dout * (size_t)Ln2 * sizeof(u64))) return EXACTO_ERR_HIP;
+    }
     if (hps_sum) {
         if (grow((u64**)&c->d_dall, &c->dall_cap, std::max<size_t>((size_t)P * gu * c->n * sizeof(int16_t), 8)) ||
             grow((u64**)&c->d_dk, &c->dk_cap, std::max<size_t>(Bd * gu * c->n * 2, 8)) ||
@@ -2330,7 +2409,8 @@ static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
         c->chain_coef_bytes = ccap;
         c->coef_out = c->chain_coef + (size_t)c->coef_slot * c->coef_slot_words;
     }
-    u64* cf = psum && c->coef_out ? c->coef_out : out;
+    const bool chain_cf = psum && c->coef_out;
+    u64* cf = chain_cf ? c->coef_out : grouped ? c->gsum_buf : out;
     c->coef_written = false;
     if (psum) {
         c->psum.on = true;
@@ -2343,7 +2423,7 @@ static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
     }
     bool coef = false;
     if (op.ea) {
-        c->tensor_share_d = (int)d;
+        c->tensor_share_d = (int)((na + nb + 1) / 2);
         c->tensor_share_npairs = npairs;
     }
     const int rc = run_mul(c, op, P, c->prod, Ln2, true, &coef);
@@ -2356,7 +2436,7 @@ static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
     if ((sum_ks || hps_sum) && !coef) return fail(EXACTO_ERR_HIP, "internal: digit sums without a deferred key switch");
     if (!psum) {
         ProfScope pk(c, PK_COMBINE, (u64)B * dout, 8.0 * c->n * B * 2 * c->L * (double)(npairs + dout));
-        launch_dbfv_combine(c->prod, npairs, c->d_term_start, c->d_terms, out, (int)B, (int)dout, c->n, c->L,
+        launch_dbfv_combine(c->prod, npairs, c->d_term_start, c->d_terms, cf, (int)B, (int)dout, c->n, c->L,
                             c->d_primes, c->stream);
         CHECK_LAUNCH();
     }
@@ -2398,18 +2478,26 @@ static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
         db.src16_item_stride = (long)gu * c->n;
         if (int e = run_ntt(c, db, (long)Bd * gu * c->L, false)) return e;
     }
+    if (grouped) {
+        // each slot's groups added mod q_l (relinearised already, coefficient domain when `coef`): the
+        // forward transform below then runs once per slot, not once per group
+        ProfScope pg(c, PK_GROUP_SUM, (u64)B * nslots, 8.0 * c->n * B * 2 * c->L * (double)(dout + nslots));
+        launch_group_sum(cf, out, c->d_slot_start, (int)dout, (int)nslots, (long)B, c->n, c->L, c->d_primes, c->stream);
+        CHECK_LAUNCH();
+        cf = out;
+    }
     if (coef) {
-        NttBatch ob = contiguous(out, (long)B * dout, 2L * c->L, 0, c->L, c->n);
+        NttBatch ob = contiguous(out, (long)B * nslots, 2L * c->L, 0, c->L, c->n);
         ob.src = cf;   // (== out unless a chain keeps the coefficient form)
         // a chain step whose limbs stay in the coefficient domain (cf) for the next step: that step's
         // extension of its left operand (exact lift of cf to the auxiliary primes, then their forward
         // transform: extend_cts with coef = cf) is made here, and the two forward batches go in one
         // launch (cfg5: 512 + 640 polynomials instead of two launches that each fill about one
         // generation of the 512 resident workgroups)
-        const bool pre = cf != out && op.ea != nullptr && dout == d && !c->deferred_code &&
-                         c->path != EXACTO_PATH_HPS && c->ext_a_cap >= (size_t)B * d * 2 * c->K * poly_bytes(c);
+        const bool pre = chain_cf && op.ea != nullptr && dout == na && na == nb && !c->deferred_code &&
+                         c->path != EXACTO_PATH_HPS && c->ext_a_cap >= (size_t)B * na * 2 * c->K * poly_bytes(c);
         if (pre) {
-            const long cts = (long)B * d;
+            const long cts = (long)B * na;
             {
                 ProfScope pl(c, PK_LIFT, 2ull * cts, 8.0 * (c->L + c->K) * c->n * 2.0 * cts);
                 launch_exact_lift(cf, c->ext_a, 2 * cts, c->n, c->d_crt, c->d_primes, c->L, c->K, crt_mode(c),
@@ -2420,9 +2508,9 @@ static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
             if (int e = run_ntt_fwd2(c, ob, cts * 2 * c->L, eb, cts * 2 * c->K)) return e;
             c->ext_a_ready = true;
         } else {
-            if (int e = run_ntt(c, ob, (long)B * dout * 2 * c->L, false)) return e;
+            if (int e = run_ntt(c, ob, (long)B * nslots * 2 * c->L, false)) return e;
         }
-        c->coef_written = cf != out;
+        c->coef_written = chain_cf;
     }
     if (hps_sum) {
         ProfScope pm(c, PK_RELIN_MAC, (u64)Bd, 8.0 * c->n * c->L * Bd * (4.0 + gu));
@@ -2431,6 +2519,14 @@ static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
         CHECK_LAUNCH();
     }
     return 0;
+}
+
+// out = [B][dout][2][L][n] for the output limbs `limbs` (dout = limbs.size()), one group of items
+static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* a,
+                          const uint64_t* b, uint64_t* out, size_t B, bool b_extended,
+                          const std::vector<int>* limbs) {
+    if (int e = dbfv_plan(c, B, d, base, plain, *limbs)) return e;
+    return mul_group_run(c, d, d, a, b, out, B, b_extended, limbs->size(), limbs->size(), &c->last_dbfv_ks);
 }
 
 // Every buffer of a dbfv_mul pass grows with its item count (the products' results and digits, their
@@ -2549,6 +2645,145 @@ extern "C" int exacto_dbfv_mul_limbs(exacto_ctx* c, size_t d, uint64_t base, uin
                      [&](std::vector<u64*>& in, u64* o) {
                          return exacto_dbfv_mul_limbs_dev(c, d, base, plain, in[0], in[1], o, B, limbs, nlimbs);
                      });
+}
+
+// ============================================================== sums of ciphertext products
+
+// How many products of one output bfv_mul_sum key-switches as one sum on this context: what the
+// resident key's 31-bit basis (or the wide one) lifts, what the summed scale takes where it runs
+// (psum_max), and the caller's limit `cap` (0: none).  0: this context has no summed key switch (no
+// 31-bit basis, gadget base above 2^16, small n, EXACTO_KS32=0, HPS, schoolbook): one per product.
+// want > 0 (a bfv_mul_sum about to run sums of `want`): the primary basis is chosen for them first,
+// as dbfv_mul does for its limbs.
+static int mul_sum_group_max(exacto_ctx* c, int want, size_t cap, int* gmax) {
+    *gmax = 0;
+    const size_t gu = std::min<size_t>(c->G, c->rlk_keys);
+    if (want > c->ks32_need_m) {
+        c->ks32_need_m = want;
+        if (c->rs_valid && c->ks32_lazy_active && want > c->ks32_sum_max) c->rs_valid = false;
+    }
+    const bool on = c->S32 > 0 && c->ks32 && c->digit16 && c->gbase <= 65536 && c->rlk_loaded && gu > 0 &&
+                    !c->deferred_code;
+    if (!on) return 0;
+    if (int e = ensure_rs(c)) return e;
+    int g = std::max(c->ks32_sum_max, c->kw.S > 0 ? c->kw.sum_max : 0);
+    bool near60 = c->ntt_asm && c->ntt_asm_inv;
+    for (u64 q : c->primes) near60 &= q < (1ull << 60) && q > (1ull << 60) - (1ull << 24);
+    const bool psum = c->psum_env && c->psum_max >= 1 && c->share_ext && c->K > 0 && near60 &&
+                      (c->logn == 12 || c->logn == 13) && exact_scale_sp_ok(c->L, c->K, crt_mode(c));
+    if (psum) g = std::min(g, c->psum_max);
+    if (cap) g = (int)std::min<size_t>((size_t)g, cap);
+    *gmax = std::max(g, 0);
+    return 0;
+}
+
+// One context's share of a bfv_mul_sum batch: items in passes of whole items within
+// EXACTO_DBFV_GROUP_MB (as dbfv_mul_core), each pass one plan and one mul_group_run.  mmax: the most
+// terms of one slot; cap: the caller's group limit (the parent context's when this is a twin).
+static int mul_sum_core(exacto_ctx* c, const u64* a, size_t na, const u64* b, size_t nb, const uint32_t* ia,
+                        const uint32_t* ib, const uint32_t* slot, size_t nterms, size_t nslots, size_t mmax, size_t cap,
+                        u64* out, size_t B) {
+    // chain state belongs to chains: this call neither reads a previous step's carry nor leaves one
+    c->coef_in = nullptr;
+    c->coef_slot = -1;
+    c->ext_a_ready = false;
+    int gmax = 0;
+    if (int e = mul_sum_group_max(c, (int)std::min<size_t>(cap ? std::min(cap, mmax) : mmax, 64), cap, &gmax)) return e;
+    // every slot within one group: one group per slot and no extra pass; no summed key switch: the
+    // per-product path sums any number of products (launch_dbfv_combine)
+    const size_t gcap = gmax >= 1 && mmax > (size_t)gmax ? (size_t)gmax : 0;
+    size_t ngroups = nslots;
+    if (gcap) {
+        std::vector<size_t> cnt(nslots, 0);
+        for (size_t t = 0; t < nterms; ++t) ++cnt[slot[t]];
+        ngroups = 0;
+        for (size_t s = 0; s < nslots; ++s) ngroups += (cnt[s] + gcap - 1) / gcap;
+    }
+    const size_t n = c->n, L = c->L, K = c->K, G = c->G, S = std::max(c->S32, c->kw.S);
+    const size_t per_item = 8 * n * (nterms * 2 * L + (na + nb) * 2 * K) +              // products, both extensions
+                            n * G * (nterms * 2 + ngroups * (4 + 4 * S)) +              // digits, sums, residues
+                            4 * n * ngroups * 2 * L * S +                               // key-switch sums
+                            (ngroups > nslots ? 8 * n * ngroups * 2 * L : 0);           // the groups' results
+    const size_t Bg = std::max<size_t>(1, c->dbfv_group_bytes / std::max<size_t>(per_item, 1));
+    const size_t ctw = 2 * L * n;
+    for (size_t g0 = 0; g0 < B; g0 += Bg) {
+        const size_t cnt = std::min(Bg, B - g0);
+        if (int e = mul_sum_plan(c, cnt, na, nb, ia, ib, slot, nterms, nslots, gcap)) return e;
+        if (int e = mul_group_run(c, na, nb, a + g0 * na * ctw, b + g0 * nb * ctw, out + g0 * nslots * ctw, cnt, false,
+                                  (size_t)c->cached_ngroups, nslots, &c->last_mul_sum_mode))
+            return e;
+    }
+    return 0;
+}
+
+// out[b][s] = sum over the terms t with slot[t] == s of bfv_mul_and_relin(a[b][ia[t]], b[b][ib[t]])
+// (eval.rs:73-82 per product, bfv_add eval.rs:14-32 over the terms): the sums move in front of the key
+// switch and the forward transform (mul_group_run), in groups of what one key switch lifts.
+extern "C" int exacto_bfv_mul_sum_dev(exacto_ctx* c, const uint64_t* a, size_t na, const uint64_t* b, size_t nb,
+                                      const uint32_t* ia, const uint32_t* ib, const uint32_t* slot, size_t nterms,
+                                      size_t nslots, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (nterms == 0) return invalid_param("bfv_mul_sum: nterms = 0 (no products to sum)");
+    if (!ia || !ib || !slot) return invalid_param("bfv_mul_sum: null term list");
+    if (nterms > 0x7fffffffu / 4) return invalid_param("bfv_mul_sum: nterms = " + std::to_string(nterms) + " is too large");
+    std::vector<size_t> per_slot(nslots, 0);
+    for (size_t t = 0; t < nterms; ++t) {
+        if (ia[t] >= na)
+            return invalid_param("bfv_mul_sum: term " + std::to_string(t) + " left index " + std::to_string(ia[t]) +
+                                 " >= na = " + std::to_string(na));
+        if (ib[t] >= nb)
+            return invalid_param("bfv_mul_sum: term " + std::to_string(t) + " right index " + std::to_string(ib[t]) +
+                                 " >= nb = " + std::to_string(nb));
+        if (slot[t] >= nslots)
+            return invalid_param("bfv_mul_sum: term " + std::to_string(t) + " slot " + std::to_string(slot[t]) +
+                                 " >= nslots = " + std::to_string(nslots));
+        ++per_slot[slot[t]];
+    }
+    size_t mmax = 0;
+    for (size_t s = 0; s < nslots; ++s) {
+        if (per_slot[s] == 0) return invalid_param("bfv_mul_sum: output slot " + std::to_string(s) + " has no term");
+        mmax = std::max(mmax, per_slot[s]);
+    }
+    if (B == 0) return 0;
+    if (!a || !b || !out) return invalid_param("bfv_mul_sum: null ciphertext buffer");
+    if ((uintptr_t)out & 15) return invalid_param("bfv_mul_sum: out must be 16-byte aligned");
+    const size_t ctw = 2 * c->L * (size_t)c->n;
+    auto overlaps = [&](const u64* p, size_t cts) { return out < p + B * cts * ctw && p < out + B * nslots * ctw; };
+    if (overlaps(a, na) || overlaps(b, nb)) return invalid_param("bfv_mul_sum: out overlaps an input");
+    if (c->deferred_code) return fail(c->deferred_code, c->deferred_msg);
+    if (!c->rlk_loaded) return fail(EXACTO_ERR_MISSING_KEY, "key not available: relinearization key not loaded");
+    const size_t cap = c->mul_sum_cap;
+    // two parts on two streams, as exacto_dbfv_mul_dev (split_run's measurements)
+    return split_run(c, B, 2, [&](exacto_ctx* x, size_t i0, size_t cnt) {
+        return mul_sum_core(x, a + i0 * na * ctw, na, b + i0 * nb * ctw, nb, ia, ib, slot, nterms, nslots, mmax, cap,
+                            out + i0 * nslots * ctw, cnt);
+    });
+}
+
+extern "C" int exacto_bfv_mul_sum(exacto_ctx* c, const uint64_t* a, size_t na, const uint64_t* b, size_t nb,
+                                  const uint32_t* ia, const uint32_t* ib, const uint32_t* slot, size_t nterms,
+                                  size_t nslots, uint64_t* out, size_t B) {
+    if (!c) return invalid_param("null context");
+    const size_t ctb = 2 * c->L * poly_bytes(c);
+    return host_call(c, {{a, B * na * ctb}, {b, B * nb * ctb}}, B * nslots * ctb, out,
+                     [&](std::vector<u64*>& in, u64* o) {
+                         return exacto_bfv_mul_sum_dev(c, in[0], na, in[1], nb, ia, ib, slot, nterms, nslots, o, B);
+                     });
+}
+
+extern "C" int exacto_ctx_set_mul_sum_group(exacto_ctx* c, size_t max_products) {
+    if (!c) return invalid_param("null context");
+    c->mul_sum_cap = max_products;
+    return 0;
+}
+
+extern "C" int exacto_bfv_mul_sum_info(exacto_ctx* c, size_t* group_max, int* last_mode) {
+    if (int e = check_ctx(c)) return e;
+    int gmax = 0;
+    if (int e = mul_sum_group_max(c, 0, c->mul_sum_cap, &gmax)) return e;
+    if (group_max) *group_max = (size_t)std::max(gmax, 1);   // (no summed key switch: one product each)
+    if (last_mode) *last_mode = c->last_mul_sum_mode;
+    return 0;
 }
 
 // ============================================================== decryption

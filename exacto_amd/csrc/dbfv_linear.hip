@@ -93,4 +93,67 @@ void launch_dbfv_linmap(const u64* in, u64* out, const LinTerm* terms, int E, in
     }
 }
 
+// bfv_mul_sum's group sum: an output slot whose products exceed what one key switch lifts is computed
+// as several groups (each one summed scale and one summed key switch); this adds a slot's groups
+// modulo q_l before the slot's forward transform.  in [B][groups][rpi][n] with rpi = 2 L, out
+// [B][nslots][rpi][n], slot s = groups [slot_start[s], slot_start[s + 1]) (at least one each).  Same
+// shape as the linear map above: a thread owns two adjacent coefficients of one (item, slot,
+// component, limb) row, 16-byte accesses, the next group's load issued before the current add; every
+// input is read once and every output written once.
+template <bool WIDE>
+__global__ void __launch_bounds__(LM_TPB)
+group_sum_kernel(const u64* __restrict__ in, u64* __restrict__ out, const int* __restrict__ slot_start, int groups,
+                 int nslots, int rpi, int L, int n, long rows, const PrimeConst* __restrict__ primes) {
+    long row;
+    int j;
+    if (WIDE) {
+        const int bpr = n / LM_SLOTS;
+        row = blockIdx.x / bpr;
+        j = (int)(blockIdx.x - row * bpr) * LM_SLOTS + 2 * (int)threadIdx.x;
+    } else {
+        const long g = ((long)blockIdx.x * LM_TPB + threadIdx.x) * 2;
+        row = g / n;
+        j = (int)(g - row * n);
+    }
+    if (row >= rows) return;
+    // row = (item * nslots + slot) * rpi + r
+    const long is = row / rpi;
+    const int r = (int)(row - is * rpi);
+    const long item = is / nslots;
+    const int slot = (int)(is - item * nslots);
+    const u64 q = primes[r % L].q;
+    const int g0 = slot_start[slot], g1 = slot_start[slot + 1];
+    const long group_stride = (long)rpi * n;
+    const u64* src = in + ((item * groups + g0) * rpi + r) * n + j;
+    ulonglong2 acc = lm_load(src);
+    if (g0 + 1 < g1) {
+        ulonglong2 x = lm_load(src + group_stride);
+        for (int g = g0 + 1; g < g1; ++g) {
+            ulonglong2 xn = x;
+            if (g + 1 < g1) xn = lm_load(src + (long)(g + 1 - g0) * group_stride);
+            acc.x = add_mod(acc.x, x.x, q);
+            acc.y = add_mod(acc.y, x.y, q);
+            x = xn;
+        }
+    }
+    *reinterpret_cast<ulonglong2*>(out + row * n + j) = acc;
+}
+
+// n even, rows = items * nslots * 2 L, rows * n / 2 threads; in and out 16-byte aligned, disjoint
+void launch_group_sum(const u64* in, u64* out, const int* slot_start, int groups, int nslots, long items, int n, int L,
+                      const PrimeConst* primes, hipStream_t s) {
+    const int rpi = 2 * L;
+    const long rows = items * nslots * rpi;
+    if (rows == 0) return;
+    if (n % LM_SLOTS == 0) {
+        const long blocks = rows * (n / LM_SLOTS);
+        EXACTO_LAUNCH(group_sum_kernel<true>, dim3((unsigned)blocks), dim3(LM_TPB), 0, s, in, out, slot_start, groups,
+                      nslots, rpi, L, n, rows, primes);
+    } else {
+        const long blocks = (rows * n / 2 + LM_TPB - 1) / LM_TPB;
+        EXACTO_LAUNCH(group_sum_kernel<false>, dim3((unsigned)blocks), dim3(LM_TPB), 0, s, in, out, slot_start, groups,
+                      nslots, rpi, L, n, rows, primes);
+    }
+}
+
 }  // namespace exacto

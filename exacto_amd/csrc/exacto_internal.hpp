@@ -304,6 +304,10 @@ struct __attribute__((aligned(32))) LinTerm {
 // [items][d_out][polys][L][n], both 16-byte aligned and disjoint; terms [E][L], rows in order, d_out lasts
 void launch_dbfv_linmap(const u64* in, u64* out, const LinTerm* terms, int E, int d_in, int d_out, long items,
                         int polys, int n, int L, const PrimeConst* primes, hipStream_t s);
+// out[item][s] = sum mod q_l of in[item][g], g in [slot_start[s], slot_start[s + 1]) (bfv_mul_sum's groups
+// of one output slot); in [items][groups][2][L][n], out [items][nslots][2][L][n], 16-byte aligned, disjoint
+void launch_group_sum(const u64* in, u64* out, const int* slot_start, int groups, int nslots, long items, int n, int L,
+                      const PrimeConst* primes, hipStream_t s);
 
 // ---- plaintext-ciphertext operations (plain.hip) ----
 enum { PLAIN_MUL = 0, PLAIN_ADD = 1 };

@@ -227,6 +227,30 @@ inline BfvCiphertext bfv_mul_and_relin(const BfvCiphertext& a, const BfvCipherte
     return bfv_mul_and_relin(std::vector<BfvCiphertext>{a}, std::vector<BfvCiphertext>{b}, rlk)[0];
 }
 
+// Sums of ciphertext products with one key switch per sum (exacto_bfv_mul_sum; the ciphertext x
+// ciphertext counterpart of bfv_inner_product): out[s] = sum over the terms {ia, ib, s} of
+// bfv_mul_and_relin(a[ia], b[ib], rlk), bit for bit the composition with bfv_add.  One item; a and b
+// may be the same vector, a pair listed twice counts twice.
+struct MulSumTerm {
+    uint32_t ia, ib, slot;
+};
+inline std::vector<BfvCiphertext> bfv_mul_sum(const std::vector<BfvCiphertext>& a, const std::vector<BfvCiphertext>& b,
+                                              const std::vector<MulSumTerm>& terms, size_t nslots,
+                                              const RelinKey& rlk) {
+    if (a.empty() || b.empty()) throw ExactoError(1, "invalid parameter: bfv_mul_sum needs ciphertexts on both sides");
+    const BfvParamsPtr& prm = a[0].params;
+    if (a[0].c.size() != 2 || b[0].c.size() != 2)
+        throw ExactoError(1, "invalid parameter: multiplication requires degree-1 ciphertexts");
+    detail::load_key(rlk);
+    auto fa = detail::flatten(a, 2), fb = detail::flatten(b, 2);
+    std::vector<uint32_t> ia, ib, sl;
+    for (auto& t : terms) { ia.push_back(t.ia); ib.push_back(t.ib); sl.push_back(t.slot); }
+    std::vector<uint64_t> out(nslots * 2 * prm->num_limbs() * prm->ring_degree);
+    detail::check(exacto_bfv_mul_sum(prm->ctx(), fa.data(), a.size(), fb.data(), b.size(), ia.data(), ib.data(),
+                                     sl.data(), terms.size(), nslots, out.data(), 1));
+    return detail::unflatten(out, nslots, 2, prm);
+}
+
 // bfv_add / bfv_sub (eval.rs:14-51): each batch has one component count; the two counts may differ
 // (the longer operand's extra components pass through, ct2's negated under subtraction)
 namespace detail {

@@ -216,6 +216,43 @@ int exacto_dbfv_mul_limbs_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t
                               const uint64_t* a, const uint64_t* b, uint64_t* out, size_t batch, const uint32_t* limbs,
                               size_t nlimbs);
 
+/* Sums of ciphertext products with one key switch per sum (the ciphertext x ciphertext counterpart of
+ * exacto_bfv_inner_product: dot products, matrix-vector products, convolutions).  For every batch
+ * item and output slot s,
+ *     out[item][s] = sum over the terms t with slot[t] == s of
+ *                    bfv_mul_and_relin(a[item][ia[t]], b[item][ib[t]], rlk)      (eval.rs:73-82)
+ * added with bfv_add (eval.rs:14-32): bit for bit what exacto_bfv_mul_and_relin per product and
+ * exacto_bfv_add per term give, but the sums are taken before the key switch and the forward
+ * transform, so each output pays them once (relinearisation is linear mod q in the gadget digits).
+ * a = [B][na][2][L][n], b = [B][nb][2][L][n], out = [B][nslots][2][L][n], NTT domain.  ia, ib, slot:
+ * HOST arrays of nterms entries, for the _dev form too.  a and b may be the same buffer (sums of
+ * squares); a pair listed twice counts twice.  out must not overlap an input and is 16-byte aligned.
+ * The resident relinearisation key and min(G, num_keys) digits are used as by
+ * exacto_bfv_mul_and_relin; with no key, and on a context with a deferred parameter error, the error
+ * is that function's.  InvalidParam: nterms == 0, an index >= na or >= nb, a slot >= nslots, an
+ * output slot with no term.  batch == 0 returns 0.
+ * A slot with more products than one key switch lifts (exacto_bfv_mul_sum_info) is computed in groups
+ * whose coefficient-domain results are added before the slot's forward transform.  Contexts without
+ * the summed key switch (no 31-bit basis, gadget base above 2^16, small n, HPS, schoolbook) take one
+ * key switch per product and sum the results.
+ * The _dev form is asynchronous on the context's stream; a call whose term lists and shape differ
+ * from the previous call's may wait for the stream once before it uploads its tables. */
+int exacto_bfv_mul_sum(exacto_ctx* ctx, const uint64_t* a, size_t na, const uint64_t* b, size_t nb,
+                       const uint32_t* ia, const uint32_t* ib, const uint32_t* slot, size_t nterms, size_t nslots,
+                       uint64_t* out, size_t batch);
+int exacto_bfv_mul_sum_dev(exacto_ctx* ctx, const uint64_t* a, size_t na, const uint64_t* b, size_t nb,
+                           const uint32_t* ia, const uint32_t* ib, const uint32_t* slot, size_t nterms, size_t nslots,
+                           uint64_t* out, size_t batch);
+/* At most max_products products of one output are key-switched as one sum (0: the context's own
+ * limit).  Results do not depend on it. */
+int exacto_ctx_set_mul_sum_group(exacto_ctx* ctx, size_t max_products);
+/* group_max: how many products of one output a bfv_mul_sum key-switches as one sum, with the resident
+ * key, the basis in use and the limit set above (1 where the context has no summed key switch).
+ * last_mode: the last bfv_mul_sum's key switch in the codes of exacto_ctx_info's dbfv_key_switch (1 =
+ * summed in the primary 31-bit basis, 2 = summed in the wide basis, 0 = one per product), -1 = none
+ * yet.  Either pointer may be null. */
+int exacto_bfv_mul_sum_info(exacto_ctx* ctx, size_t* group_max, int* last_mode);
+
 /* dBFV multiplication chain, device-resident (paper_repro.rs:203-236 guard-bypass semantics;
  * bfv_host.rs:258-288 without the bootstrap): out = (((x*y)*y)...*y), `depth` dbfv_mul steps,
  * each with both inputs' mul_depth reset to 0, intermediates kept in context-owned HBM buffers.
