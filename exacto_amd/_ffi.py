@@ -99,6 +99,8 @@ _SIGS = [
     ("exacto_dbfv_decrypt_poly", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
     ("exacto_dbfv_decrypt_poly_dev", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
     ("exacto_dbfv_mul_chain_dev", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ, _SZ], C.c_int),
+    ("exacto_bfv_mod_switch", [_P, _P, _SZ, _SZ, _SZ, C.c_int, _P, _SZ], C.c_int),
+    ("exacto_bfv_mod_switch_dev", [_P, _P, _SZ, _SZ, _SZ, C.c_int, _P, _SZ], C.c_int),
     ("exacto_bfv_noise", [_P, _P, _SZ, _P, _P, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_noise_dev", [_P, _P, _SZ, _P, _P, _P, _P, _SZ], C.c_int),
     ("exacto_dbfv_noise", [_P, _SZ, _P, _P, _P, _SZ], C.c_int),
@@ -1025,6 +1027,50 @@ class HipContext:
         gm, md = _SZ(0), C.c_int(-1)
         check(self._lib.exacto_bfv_mul_sum_info(self._h, C.byref(gm), C.byref(md)))
         return {"group_max": int(gm.value), "last_mode": int(md.value)}
+
+    # ---- modulus switching (exacto_bfv_mod_switch)
+    MOD_SWITCH_MODES = {"round": 0, "reference": 1}
+
+    @classmethod
+    def _mod_switch_args(cls, polys, limbs_in, limbs_out, mode, batch):
+        """Malformed arguments are rejected here, before any library call (the library checks limbs_in
+        against the context's L, and the buffers)."""
+        if mode not in cls.MOD_SWITCH_MODES:
+            raise ValueError(f"bfv_mod_switch: mode = {mode!r} (need one of {sorted(cls.MOD_SWITCH_MODES)})")
+        for name, v in (("polys", polys), ("limbs_in", limbs_in), ("limbs_out", limbs_out), ("batch", batch)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError(f"bfv_mod_switch: {name} = {v!r} (need a non-negative integer)")
+        if polys < 1:
+            raise ValueError("bfv_mod_switch: the ciphertext has no polynomials")
+        if limbs_in < 2:
+            raise ValueError(f"bfv_mod_switch: limbs_in = {limbs_in}: cannot drop prime: only one modulus remaining")
+        if not 1 <= limbs_out < limbs_in:
+            raise ValueError(f"bfv_mod_switch: limbs_out = {limbs_out} (need 1 <= limbs_out < limbs_in = {limbs_in})")
+        return cls.MOD_SWITCH_MODES[mode]
+
+    def bfv_mod_switch(self, ct: np.ndarray, limbs_out=None, mode="round") -> np.ndarray:
+        """Drop the top primes of ct [B][polys][limbs_in][n] (over the context's first limbs_in primes) down to
+        limbs_out (default: one drop) -> [B][polys][limbs_out][n], a ciphertext of a context created with
+        moduli[:limbs_out].  mode "round": exact rounding division by each dropped prime; "reference": the
+        reference's drop_last_rns_prime literally (unscaled)."""
+        if not isinstance(ct, np.ndarray) or ct.ndim != 4:
+            raise ValueError("bfv_mod_switch: ct must be a [B][polys][limbs_in][n] array")
+        B, polys, lin, n = ct.shape
+        if n != self.n:
+            raise ValueError(f"bfv_mod_switch: ct has rows of {n} coefficients, the context n = {self.n}")
+        lout = lin - 1 if limbs_out is None else limbs_out
+        m = self._mod_switch_args(polys, lin, lout, mode, B)
+        ct = _u64(ct)
+        out = np.zeros((B, polys, int(lout), n), dtype=np.uint64)
+        check(self._lib.exacto_bfv_mod_switch(self._h, ct.ctypes.data, polys, lin, int(lout), m, out.ctypes.data, B))
+        return out
+
+    def bfv_mod_switch_dev(self, ct, polys, limbs_in, limbs_out, out, batch, mode="round"):
+        """Device buffers ct [batch][polys][limbs_in][n] -> out [batch][polys][limbs_out][n] (disjoint, 16-byte
+        aligned).  Asynchronous on the context's stream."""
+        m = self._mod_switch_args(polys, limbs_in, limbs_out, mode, batch)
+        check(self._lib.exacto_bfv_mod_switch_dev(self._h, self._p(ct), int(polys), int(limbs_in), int(limbs_out), m,
+                                                  self._p(out), int(batch)))
 
     # ---- RCCL collectives (exacto_hip.h; comm = RcclComm)
     def broadcast_relin_key(self, comm: "RcclComm", root: int, num_keys: int):

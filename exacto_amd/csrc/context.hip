@@ -388,6 +388,11 @@ struct exacto_ctx {
     int* d_slot_start = nullptr;     // ... and, when a slot has several, slot s = groups [start[s], start[s+1])
     u64* gsum_buf = nullptr;         // bfv_mul_sum: the groups' coefficient-domain results [B][groups][2][L][n]
     size_t gsum_cap = 0;
+    // modulus switch: q_j^-1 mod q_i (j > i) at [j * L + i] with their Shoup companions, built on first use;
+    // the intermediate levels of a call that drops several primes (two halves, one chunk each)
+    std::vector<u64> msw_w, msw_ws;
+    u64* msw_buf = nullptr;
+    size_t msw_cap = 0;
     size_t cached_B = 0, cached_d = 0;
     u64 cached_base = 0, cached_p = 0;
     int cached_npairs = 0;
@@ -1173,7 +1178,7 @@ extern "C" void exacto_ctx_destroy(exacto_ctx* c) {
     }
     if (c->ev_twin_in) (void)hipEventDestroy(c->ev_twin_in);
     free_dev(c->io); free_dev(c->prod); free_dev(c->d_off); free_dev(c->d_term_start); free_dev(c->d_terms);
-    free_dev(c->d_slot_start); free_dev(c->gsum_buf);
+    free_dev(c->d_slot_start); free_dev(c->gsum_buf); free_dev(c->msw_buf);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     free_dev(c->boot_buf); free_dev(c->boot_slots);
     delete c;
@@ -1264,7 +1269,8 @@ extern "C" int exacto_ctx_load_relin_key(exacto_ctx* c, const uint64_t* rlk, siz
 enum ProfKind : int {
     PK_FWD = 0, PK_INV = 1, PK_TENSOR = 2, PK_POLYMUL = 3, PK_LIFT = 4, PK_SCALE = 5, PK_KS_DIGITS = 6,
     PK_KS_MAC = 7, PK_KS_CRT = 8, PK_PAIRSUM = 9, PK_PSUM_SCALE = 10, PK_TENSOR_C2 = 11, PK_DIGIT_SUM = 12,
-    PK_COMBINE = 13, PK_HPS_EXT = 14, PK_RELIN_MAC = 15, PK_HPS_SCALE = 16, PK_GROUP_SUM = 17, PK_COUNT = 18
+    PK_COMBINE = 13, PK_HPS_EXT = 14, PK_RELIN_MAC = 15, PK_HPS_SCALE = 16, PK_GROUP_SUM = 17, PK_MODSWITCH = 18,
+    PK_COUNT = 19
 };
 
 struct ProfScope {
@@ -2867,6 +2873,96 @@ extern "C" int exacto_dbfv_decrypt_poly(exacto_ctx* c, size_t d, uint64_t base, 
                      [&](std::vector<u64*>& dv, u64* o) {
                          return exacto_dbfv_decrypt_poly_dev(c, d, base, plain, dv[0], dv[1], o, B);
                      });
+}
+
+// ============================================================== modulus switch (bfv/modswitch.rs)
+
+// Argument checks shared by both forms, before anything is launched or copied.
+static int mod_switch_check(const exacto_ctx* c, size_t polys, size_t lin, size_t lout, int mode) {
+    if (lin <= 1) return invalid_param("cannot drop prime: only one modulus remaining");
+    if (lin > (size_t)c->L)
+        return invalid_param("mod_switch: limbs_in = " + std::to_string(lin) + " exceeds the context's " +
+                             std::to_string(c->L) + " ciphertext primes");
+    if (lout == 0) return invalid_param("mod_switch: limbs_out = 0 (at least one prime must remain)");
+    if (lout >= lin)
+        return invalid_param("mod_switch: limbs_out = " + std::to_string(lout) + " must be below limbs_in = " +
+                             std::to_string(lin));
+    if (polys == 0) return invalid_param("mod_switch: ciphertext has no polynomials");
+    if (mode != EXACTO_MODSWITCH_ROUND && mode != EXACTO_MODSWITCH_REFERENCE)
+        return invalid_param("mod_switch: unknown mode " + std::to_string(mode));
+    return 0;
+}
+
+// One drop l -> l - 1 of `rows` polynomials; the kernel path is chosen from the primes involved
+// (0 .. l-1), as run_ntt chooses the transforms'.
+static int run_drop_prime(exacto_ctx* c, const u64* in, u64* out, size_t rows, int l, bool round) {
+    const int L = c->L;
+    if (c->msw_w.empty()) {
+        c->msw_w.assign((size_t)L * L, 0);
+        c->msw_ws.assign((size_t)L * L, 0);
+        for (int j = 1; j < L; ++j)
+            for (int i = 0; i < j; ++i) {
+                const u64 qi = c->ctq[i], w = invmod_h(c->ctq[j] % qi, qi);
+                c->msw_w[(size_t)j * L + i] = w;
+                c->msw_ws[(size_t)j * L + i] = shoup_h(w, qi);
+            }
+    }
+    DropPrimeK K{};
+    for (int i = 0; i < l - 1; ++i) {
+        K.w[i] = c->msw_w[(size_t)(l - 1) * L + i];
+        K.ws[i] = c->msw_ws[(size_t)(l - 1) * L + i];
+    }
+    bool lazy = true, near60 = c->ntt_asm && c->ntt_asm_inv;
+    for (int t = 0; t < l; ++t) {
+        lazy &= c->primes[t] < (1ull << 60);
+        near60 &= c->primes[t] < (1ull << 60) && c->primes[t] > (1ull << 60) - (1ull << 32);
+    }
+    // algorithmic bytes: l rows read, l - 1 written
+    ProfScope ps(c, PK_MODSWITCH, (u64)rows, 8.0 * c->n * (double)rows * (2 * l - 1));
+    launch_drop_prime(in, out, (long)rows, l, round, K, c->logn, lazy, near60, c->d_primes, c->stream);
+    CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int exacto_bfv_mod_switch_dev(exacto_ctx* c, const uint64_t* ct, size_t polys, size_t lin, size_t lout,
+                                         int mode, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = mod_switch_check(c, polys, lin, lout, mode)) return e;
+    if (B == 0) return 0;
+    if (!ct || !out) return invalid_param("mod_switch: null ciphertext buffer");
+    if (((uintptr_t)ct | (uintptr_t)out) & 15) return invalid_param("mod_switch: ct and out must be 16-byte aligned");
+    const size_t n = (size_t)c->n, iw = polys * lin * n, ow = polys * lout * n;
+    if (out < ct + B * iw && ct < out + B * ow) return invalid_param("mod_switch: out overlaps ct");
+    const bool round = mode == EXACTO_MODSWITCH_ROUND;
+    if (lin - lout == 1) return run_drop_prime(c, ct, out, B * polys, (int)lin, round);
+    // several drops: chunk by chunk through two halves of the workspace, the last drop into out
+    const size_t C = std::min(c->chunk, B), half = C * polys * (lin - 1) * n;
+    if (grow(&c->msw_buf, &c->msw_cap, 2 * half * sizeof(u64))) return EXACTO_ERR_HIP;
+    for (size_t i0 = 0; i0 < B; i0 += C) {
+        const size_t cnt = std::min(C, B - i0);
+        const u64* src = ct + i0 * iw;
+        int h = 0;
+        for (size_t l = lin; l > lout; --l) {
+            u64* dst = l - 1 == lout ? out + i0 * ow : c->msw_buf + h * half;
+            if (int e = run_drop_prime(c, src, dst, cnt * polys, (int)l, round)) return e;
+            src = dst;
+            h ^= 1;
+        }
+    }
+    return 0;
+}
+
+extern "C" int exacto_bfv_mod_switch(exacto_ctx* c, const uint64_t* ct, size_t polys, size_t lin, size_t lout, int mode,
+                                     uint64_t* out, size_t B) {
+    if (!c) return invalid_param("null context");
+    if (int e = mod_switch_check(c, polys, lin, lout, mode)) return e;
+    if (B == 0) return 0;
+    if (!ct || !out) return invalid_param("mod_switch: null ciphertext buffer");
+    const size_t iw = polys * lin * (size_t)c->n, ow = polys * lout * (size_t)c->n;
+    if (out < ct + B * iw && ct < out + B * ow) return invalid_param("mod_switch: out overlaps ct");
+    return host_call(c, {{ct, B * iw * sizeof(u64)}}, B * ow * sizeof(u64), out, [&](std::vector<u64*>& in, u64* o) {
+        return exacto_bfv_mod_switch_dev(c, in[0], polys, lin, lout, mode, o, B);
+    });
 }
 
 // ============================================================== noise (paper_repro.rs:238-281)

@@ -176,6 +176,16 @@ bool launch_polymul(const u64* A, const u64* B, u64* out, long rows, int period,
 // out = INTT(A (.) B) row by row ([rows][n], row r mod prime r % period); out may alias A or B
 void launch_mul_inv(const u64* A, const u64* B, u64* out, long rows, int period, int logn, bool lazy, bool asm_inv,
                     const PrimeConst* primes, hipStream_t s);
+// Modulus switch, one drop (ntt.hip): rows polynomials [l][n] over primes 0 .. l-1 (NTT domain) ->
+// [l-1][n], the last prime dropped.  round: out_i = (c_i - delta) q^-1 mod q_i with delta the centred
+// residue mod q = q_{l-1}, and C the Shoup pairs of q^-1 mod q_i (i < l - 1); otherwise the
+// reference's unscaled, uncentred subtraction (C unused).  in and out must not overlap.
+// asm_rounds: n = 4096 / 8192 and primes 0 .. l-1 all in (2^60 - 2^32, 2^60); lazy: all below 2^60.
+struct DropPrimeK {
+    u64 w[EXACTO_MAX_L], ws[EXACTO_MAX_L];
+};
+void launch_drop_prime(const u64* in, u64* out, long rows, int l, bool round, const DropPrimeK& C, int logn, bool lazy,
+                       bool asm_rounds, const PrimeConst* primes, hipStream_t s);
 // p2only: every component of the ciphertext primes, the third only of the auxiliary primes (dBFV
 // psum; asm_inv and n = 4096 / 8192 only)
 void launch_inv_tensor(const Operands& op, const u64* extP, u64* T, int items, int logn, int L, int K, bool lazy,

@@ -1240,6 +1240,160 @@ bool launch_polymul(const u64* A, const u64* B, u64* out, long rows, int period,
     return true;
 }
 
+// ---------------------------------------------------------------- modulus switch: drop the last prime
+
+// One polynomial [l][n] (NTT domain, primes 0 .. l-1) -> [l-1][n] per workgroup (bfv/modswitch.rs
+// drop_last_rns_prime, and its exact form).  The last limb is inverse-transformed under q = q_{l-1};
+// the inverse leaves coefficient tid + k n/16 in d[k], which is the forward's input layout, so d stays
+// in registers while for each remaining prime q_i it is reduced to a residue, forward-transformed,
+// subtracted from c_i and (ROUND) multiplied by q^-1 mod q_i: l rows read, l - 1 written, and the
+// coefficient-domain polynomial never leaves the chip.
+//   ROUND:     d = the centred residue of x mod q (two's complement), out_i = (c_i - d) q^-1 mod q_i
+//   otherwise: d = x mod q in [0, q) (the reference's "simplified" form), out_i = c_i - d mod q_i
+//
+// n = 4096 / 8192, every prime involved in (2^60 - 2^32, 2^60): the generated rounds.  |d| < 2^59 < q_i
+// and q < 2^60 < 2 q_i, so either re-reduction is one conditional addition / subtraction.  d is held
+// across the forward transforms as ntt_polymul_kernel holds xa: 2 waves per SIMD.
+// (d parked in a second LDS image instead, each thread re-reading its own 16 values per prime: the same
+// 2 waves per SIMD, since two images allow 2 workgroups per CU at n = 4096 and 1 at 8192; measured
+// 0.186-0.188 vs 0.186-0.188 ms at cfg3 and 0.133 vs 0.126 ms at cfg5's basis, and was removed)
+template <int LOGN, bool ROUND>
+__global__ void __launch_bounds__((1 << LOGN) / 16) __attribute__((amdgpu_waves_per_eu(2)))
+ntt_dropprime_asm_kernel(const u64* in, u64* out, int l, DropPrimeK C, const PrimeConst* __restrict__ primes) {
+    constexpr int N = 1 << LOGN;
+    __shared__ u64 lds[N];
+    const int tid = threadIdx.x;
+    const long p = blockIdx.x;
+    const u64* src = in + p * l * N;
+    u64* dst = out + p * (l - 1) * N;
+    const PrimeConst& PL = primes[l - 1];
+    const u64 q = PL.q;
+    u64 d[16];
+    load_evals<N>(d, src + (long)(l - 1) * N, tid);
+    const AsmK AK = make_asmk_inv(PL);
+    inv_rounds_asm<LOGN, 0>(d, lds, tid, tw_table(PL.tw_inv), AK);   // canonical
+    if constexpr (ROUND) {
+        const u64 h = q >> 1;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) d[k] = d[k] > h ? d[k] - q : d[k];
+    }
+    for (int i = 0; i < l - 1; ++i) {
+        const PrimeConst& P = primes[i];
+        const u64 qi = P.q;
+        u64 x[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if constexpr (ROUND) x[k] = (i64)d[k] < 0 ? d[k] + qi : d[k];
+            else x[k] = d[k] >= qi ? d[k] - qi : d[k];
+        }
+        fwd_rounds_asm<LOGN, 0>(x, lds, tid, tw_table(P.tw_fwd), make_asmk(qi));   // canonical
+        const PolyRd r(src + (long)i * N, N * 8);
+        const PolyWr w(dst + (long)i * N, N * 8);
+        const u64 cw = C.w[i], cws = C.ws[i];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const u64 c = r.ld64(tid * 8, k * (N / 16) * 8);
+            u64 v = sub_mod(c, x[k], qi);
+            if constexpr (ROUND) v = shoup_mul_red(v, cw, cws, qi);
+            w.st64(v, tid * 8, k * (N / 16) * 8);
+        }
+    }
+}
+
+// Every other size and arbitrary primes (q may be far above or below q_i: a true remainder by
+// reduce64 / signed_mod; |d| < 2^61).  n = 16 runs with one live thread, as ntt_fwd_kernel.
+template <int LOGN, bool LAZY>
+__global__ void __launch_bounds__((1 << LOGN) / 16 < 64 ? 64 : (1 << LOGN) / 16)
+ntt_dropprime_kernel(const u64* in, u64* out, int l, int round, DropPrimeK C, const PrimeConst* __restrict__ primes) {
+    constexpr int N = 1 << LOGN;
+    constexpr int T = N / 16;
+    __shared__ u64 lds[N];
+    const int tid = T < 64 ? vtid() : (int)threadIdx.x;
+    if (tid >= T) return;
+    const long p = blockIdx.x;
+    const u64* src = in + p * l * N;
+    u64* dst = out + p * (l - 1) * N;
+    const PrimeConst& PL = primes[l - 1];
+    const u64 q = PL.q;
+    u64 d[16];
+    load_evals<N>(d, src + (long)(l - 1) * N, tid);
+    inv_rounds<LOGN, 0, LAZY>(d, lds, tid, tw_table(PL.tw_inv), PL);   // canonical
+    if (round) {
+        const u64 h = q >> 1;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) d[k] = d[k] > h ? d[k] - q : d[k];
+    }
+    for (int i = 0; i < l - 1; ++i) {
+        const PrimeConst& P = primes[i];
+        const u64 qi = P.q, q2 = P.two_q, q8 = 8 * qi;
+        u64 x[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            x[k] = round ? signed_mod((i64)d[k], qi, P.mu64) : reduce64(d[k], qi, P.mu64);
+        // n >= 8192: twiddles loaded next to their use (d is live across the transform: 2 or 4 waves per
+        // SIMD leave no room for a round's preloaded twiddles as well)
+        fwd_rounds<LOGN, 0, LAZY, (LOGN < 13) && EXACTO_NTT_PRELOAD>(x, lds, tid, tw_table(P.tw_fwd), (u64)0 - qi, q2,
+                                                                    q8);
+        const u64* ci = src + (long)i * N;
+        u64* oi = dst + (long)i * N;
+        const u64 cw = C.w[i], cws = C.ws[i];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            u64 v = x[k];   // [0, 16q) (LAZY) or [0, 4q) -> [0, q), as ntt_fwd_kernel
+            if (LAZY) {
+                v = v >= q8 ? v - q8 : v;
+                v = v >= 4 * qi ? v - 4 * qi : v;
+            }
+            v = v >= q2 ? v - q2 : v;
+            v = v >= qi ? v - qi : v;
+            v = sub_mod(ci[tid + k * T], v, qi);
+            if (round) v = shoup_mul_red(v, cw, cws, qi);
+            oi[tid + k * T] = v;
+        }
+    }
+}
+
+template <int LOGN>
+static void launch_dp(const u64* in, u64* out, long rows, int l, bool round, const DropPrimeK& C, bool lazy,
+                      const PrimeConst* primes, hipStream_t s) {
+    constexpr int threads = (1 << LOGN) / 16 < 64 ? 64 : (1 << LOGN) / 16;
+    if (lazy)
+        EXACTO_LAUNCH((ntt_dropprime_kernel<LOGN, true>), dim3(rows), dim3(threads), 0, s, in, out, l, (int)round, C,
+                      primes);
+    else
+        EXACTO_LAUNCH((ntt_dropprime_kernel<LOGN, false>), dim3(rows), dim3(threads), 0, s, in, out, l, (int)round, C,
+                      primes);
+}
+
+void launch_drop_prime(const u64* in, u64* out, long rows, int l, bool round, const DropPrimeK& C, int logn, bool lazy,
+                       bool asm_rounds, const PrimeConst* primes, hipStream_t s) {
+    if (rows <= 0 || l < 2) return;
+    if (asm_rounds && (logn == 12 || logn == 13)) {
+        if (logn == 12) {
+            if (round) EXACTO_LAUNCH((ntt_dropprime_asm_kernel<12, true>), dim3(rows), dim3(256), 0, s, in, out, l, C, primes);
+            else EXACTO_LAUNCH((ntt_dropprime_asm_kernel<12, false>), dim3(rows), dim3(256), 0, s, in, out, l, C, primes);
+        } else {
+            if (round) EXACTO_LAUNCH((ntt_dropprime_asm_kernel<13, true>), dim3(rows), dim3(512), 0, s, in, out, l, C, primes);
+            else EXACTO_LAUNCH((ntt_dropprime_asm_kernel<13, false>), dim3(rows), dim3(512), 0, s, in, out, l, C, primes);
+        }
+        return;
+    }
+    switch (logn) {
+        case 4: launch_dp<4>(in, out, rows, l, round, C, lazy, primes, s); break;
+        case 5: launch_dp<5>(in, out, rows, l, round, C, lazy, primes, s); break;
+        case 6: launch_dp<6>(in, out, rows, l, round, C, lazy, primes, s); break;
+        case 7: launch_dp<7>(in, out, rows, l, round, C, lazy, primes, s); break;
+        case 8: launch_dp<8>(in, out, rows, l, round, C, lazy, primes, s); break;
+        case 9: launch_dp<9>(in, out, rows, l, round, C, lazy, primes, s); break;
+        case 10: launch_dp<10>(in, out, rows, l, round, C, lazy, primes, s); break;
+        case 11: launch_dp<11>(in, out, rows, l, round, C, lazy, primes, s); break;
+        case 12: launch_dp<12>(in, out, rows, l, round, C, lazy, primes, s); break;
+        case 13: launch_dp<13>(in, out, rows, l, round, C, lazy, primes, s); break;
+        case 14: launch_dp<14>(in, out, rows, l, round, C, lazy, primes, s); break;
+        default: break;  // rejected at context creation
+    }
+}
+
 // rlk_s = floor(rlk * 2^64 / q_limb) (Shoup companions of the resident key, computed once)
 __global__ void shoup_companion_kernel(const u64* __restrict__ w, u64* __restrict__ ws, long count, int n,
                                        int L, const PrimeConst* __restrict__ primes) {

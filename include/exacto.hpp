@@ -13,6 +13,7 @@
 // Ciphertexts are host-resident here (one H2D/D2H per call); the batched overloads amortise it.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -849,6 +850,62 @@ inline Noise max_limb_noise(const DbfvCiphertext& ct, const SecretKey& sk) {
     res.words.resize(dp.bfv_params->num_limbs());
     detail::check(exacto_dbfv_noise(dp.bfv_params->ctx(), dp.num_digits, flat.data(), sk.poly.data.data(),
                                     res.words.data(), 1));
+    return res;
+}
+
+// ---- exacto::bfv::modswitch (src/bfv/modswitch.rs) and its exact form
+namespace detail {
+// `lower` continues `upper`: same n and p, ct_moduli a proper prefix of upper's
+inline bool is_lower_level(const BfvParams& upper, const BfvParams& lower) {
+    return lower.ring_degree == upper.ring_degree && lower.plain_modulus == upper.plain_modulus &&
+           !lower.ct_moduli.empty() && lower.ct_moduli.size() < upper.ct_moduli.size() &&
+           std::equal(lower.ct_moduli.begin(), lower.ct_moduli.end(), upper.ct_moduli.begin());
+}
+inline BfvCiphertext mod_switch_to(const BfvCiphertext& ct, size_t limbs_out, int mode, const BfvParamsPtr& carry) {
+    const BfvParams& prm = *ct.params;
+    const size_t polys = ct.c.size(), n = prm.ring_degree, lin = polys ? ct.c[0].num_limbs : 0;
+    auto flat = flatten({ct}, polys);
+    std::vector<uint64_t> out(polys * limbs_out * n);
+    check(exacto_bfv_mod_switch(prm.ctx(), flat.data(), polys, lin, limbs_out, mode, out.data(), 1));
+    BfvCiphertext res;
+    res.params = carry;
+    res.c.resize(polys);
+    for (size_t k = 0; k < polys; ++k) {
+        res.c[k].ring_degree = n;
+        res.c[k].num_limbs = limbs_out;
+        res.c[k].data.assign(out.begin() + (long)(k * limbs_out * n), out.begin() + (long)((k + 1) * limbs_out * n));
+    }
+    return res;
+}
+}  // namespace detail
+
+// mod_switch_drop_prime (modswitch.rs:13-34), literally: the last RNS component dropped with the
+// reference's "simplified" correction (unscaled, uncentred), the same `params` kept; the polys have
+// L - 1 limbs.  Its output does not decrypt under the smaller modulus: use mod_switch for that.
+inline BfvCiphertext mod_switch_drop_prime(const BfvCiphertext& ct) {
+    const size_t lin = ct.c.empty() ? ct.params->num_limbs() : ct.c[0].num_limbs;
+    return detail::mod_switch_to(ct, lin > 0 ? lin - 1 : 0, EXACTO_MODSWITCH_REFERENCE, ct.params);
+}
+
+// The exact modulus switch down to `lower` (ct_moduli a proper prefix of the input's, same n and p, else
+// ModulusMismatch): one rounding division per dropped prime.  The result carries `lower`, under which it
+// decrypts (with the secret key's first limbs) and multiplies (with a relinearisation key of its own:
+// gadget digits depend on Q).
+inline BfvCiphertext mod_switch(const BfvCiphertext& ct, BfvParamsPtr lower) {
+    if (!lower || !detail::is_lower_level(*ct.params, *lower))
+        throw ExactoError(EXACTO_ERR_MODULUS_MISMATCH, "modulus mismatch");
+    return detail::mod_switch_to(ct, lower->num_limbs(), EXACTO_MODSWITCH_ROUND, lower);
+}
+
+// The secret key under a lower level's parameters: its first limbs (per-prime tables depend only on (n, q_i)).
+inline SecretKey lower_secret_key(const SecretKey& sk, BfvParamsPtr lower) {
+    if (!lower || !detail::is_lower_level(*sk.params, *lower))
+        throw ExactoError(EXACTO_ERR_MODULUS_MISMATCH, "modulus mismatch");
+    SecretKey res;
+    res.params = lower;
+    res.poly.ring_degree = sk.poly.ring_degree;
+    res.poly.num_limbs = lower->num_limbs();
+    res.poly.data.assign(sk.poly.data.begin(), sk.poly.data.begin() + (long)(lower->num_limbs() * sk.poly.ring_degree));
     return res;
 }
 

@@ -313,6 +313,39 @@ int exacto_dbfv_noise(exacto_ctx* ctx, size_t d, const uint64_t* ct, const uint6
 int exacto_dbfv_noise_dev(exacto_ctx* ctx, size_t d, const uint64_t* ct, const uint64_t* sk, uint64_t* noise_out,
                           size_t batch);
 
+/* ---- modulus switching: drop ciphertext primes (bfv/modswitch.rs mod_switch_drop_prime) ----
+ * A ciphertext "at level l" (1 <= l <= L) is [B][polys][l][n] over the context's first l primes, NTT
+ * domain, the library's storage order.  The per-prime tables depend only on (n, q_i), so a level-l
+ * ciphertext is also, bit for bit, a ciphertext of a context created with moduli[:l]: decryption, noise
+ * measurement and further products happen there (with a relinearisation key generated from sk[:l]: the
+ * gadget digits depend on Q).
+ * One drop l -> l - 1, with q = q_{l-1}, Q' = q_0 ... q_{l-2} and x_j in [0, Q' q) a coefficient's CRT value:
+ *   EXACTO_MODSWITCH_ROUND      y_j = floor((2 x_j + q) / (2 q)) mod Q' = round(x_j / q) (q is odd: no ties);
+ *                               limb i = (c_i - delta) q^-1 mod q_i with delta the centred residue of
+ *                               x_j mod q.  The noise is divided by q (plus at most p + n / 2 + 2 for a
+ *                               ternary secret).
+ *   EXACTO_MODSWITCH_REFERENCE  drop_last_rns_prime literally (modswitch.rs:37-87): limb i =
+ *                               c_i - NTT_{q_i}(u mod q_i) with u = INTT_q(c_{l-1}) in [0, q), uncentred and
+ *                               unscaled.  The reference calls this "simplified"; its output does not
+ *                               decrypt under the smaller modulus.  Kept for the bit-exact seam.
+ * limbs_in -> limbs_out is limbs_in - limbs_out single drops from the top, each as above (not one
+ * rounding by the product of the dropped primes).  ct = [B][polys][limbs_in][n], out =
+ * [B][polys][limbs_out][n], polys >= 1 (a degree-2 ciphertext is switched like any other).  A dBFV
+ * ciphertext [B][d][polys][l][n] is this call with batch B * d.
+ * InvalidParam, before any launch: limbs_in <= 1 ("cannot drop prime: only one modulus remaining"),
+ * limbs_in > L, limbs_out == 0, limbs_out >= limbs_in, polys == 0, an unknown mode, out overlapping
+ * ct, a _dev buffer that is not 16-byte aligned.  batch = 0 returns 0.  The _dev form is asynchronous
+ * on the context's stream (intermediate levels of several drops live in a context-owned workspace,
+ * chunked by exacto_ctx_set_chunk). */
+enum exacto_mod_switch_mode {
+    EXACTO_MODSWITCH_ROUND = 0,
+    EXACTO_MODSWITCH_REFERENCE = 1
+};
+int exacto_bfv_mod_switch(exacto_ctx* ctx, const uint64_t* ct, size_t polys, size_t limbs_in, size_t limbs_out,
+                          int mode, uint64_t* out, size_t batch);
+int exacto_bfv_mod_switch_dev(exacto_ctx* ctx, const uint64_t* ct, size_t polys, size_t limbs_in, size_t limbs_out,
+                              int mode, uint64_t* out, size_t batch);
+
 /* ---- dBFV beyond the product: encryption, limb-wise operations, maps between digit vectors ----
  * All on the dBFV layout [B][d][polys][L][n].  DbfvCiphertext.degree is not carried over this
  * ABI; a binding keeps it (INTEGRATION.md gives the rule of each function).  Depth arrays as in
