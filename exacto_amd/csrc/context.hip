@@ -251,9 +251,9 @@ struct exacto_ctx {
     int ks32_mac_form = 0;       // ks32_mac's reduction form for the active basis (Ks32Basis::mac_form)
     Ks32Basis kw;                // wide basis (primes up to 2^31) for dBFV digit sums the primary cannot hold
     // The primary basis is one of two, chosen per relinearisation key (ensure_rs):
-    //   kn: narrow primes below 2^32 / 3 bounding |sum_g d_g * r_g| by G n (B/2) (q/2) for ANY key;
+    //   kn: narrow primes below 2^32 / 3 bounding |sum_g d_g * r_g| by G n ceil(B/2) (q/2) for ANY key;
     //   kz: lazy primes below 2^30 (cheaper 32-bit butterflies, ks32_dev.hpp), used when the resident
-    //       key's own L1 norms bound the sum: |u_{c,l}| <= (B/2) sum_g ||r_{g,c,l}||_1 < prod p / 2
+    //       key's own L1 norms bound the sum: |u_{c,l}| <= ceil(B/2) sum_g ||r_{g,c,l}||_1 < prod p / 2
     //       (a uniform key has ||r||_1 ~ n q / 4: half the generic bound).  EXACTO_KS32_LAZY=0: kn only.
     // S32 / d_p32 / d_tw32 / d_kst / ks32_sum_max / ks32_mac_form describe the active one.
     Ks32Basis kn, kz;
@@ -300,7 +300,7 @@ struct exacto_ctx {
     u64* d_hdig = nullptr;       // dBFV over HPS: the summed digits' NTT residues [B][d][G][L][n]
     size_t hdig_cap = 0;
     int16_t* d_dall = nullptr;   // dBFV: per-product digits
-    void* d_dk = nullptr;        // ... and their per-limb sums (int16, or int32 when m B/2 > 2^15 - 1)
+    void* d_dk = nullptr;        // ... and their per-limb sums (int16, or int32 when m ceil(B/2) > 2^15 - 1)
     uint32_t *d_dsk = nullptr, *d_uk = nullptr;   // their residues and key-switch sums in the 31-bit basis
     size_t dall_cap = 0, dk_cap = 0, dsk_cap = 0, uk_cap = 0;
     Prime32* d_p32 = nullptr;
@@ -569,6 +569,11 @@ static void set_shoup(u64& w, u64& ws, u64 v, u64 q) {
     ws = shoup_h(v, q);
 }
 
+// The largest magnitude of a balanced gadget digit (keyswitch.rs:24-44: a remainder >= floor(B/2)
+// becomes rem - B): ceil(B/2).  An odd base reaches -(B+1)/2, from a positive remainder equal to
+// floor(B/2); for an even base this is B/2.  (Written so that B = 2^64 - 1 does not wrap.)
+static inline u64 digit_max(u64 gbase) { return gbase / 2 + (gbase & 1); }
+
 // The largest m <= 64 with prod p > 2 m `one` + 1: the centred lift of a sum of m terms, each at most
 // `one` in magnitude, is exact.  fpc: with the float-CRT lift's margin, prod p 2^20 > (2 m one + 1)
 // (2^20 + 1), so |u| / P < 1/2 - 2^-21 against the float sum's error below 2^-48 (ks32_fpc_one).
@@ -588,8 +593,8 @@ static int sums_lifted(const Big& P, const Big& one, bool fpc) {
 }
 
 // ks32.hip's auxiliary basis: the fewest primes p == 1 mod 2n in (2^30, 2^31), largest first, with
-// prod p > 2 G n floor(B/2) floor(q_max/2) (the magnitude bound of sum_g d_g * r_g, digits balanced
-// in [-B/2, B/2), key coefficients balanced).  Eligible: exact path, gadget base <= 2^16 (int16
+// prod p > 2 G n ceil(B/2) floor(q_max/2) (the magnitude bound of sum_g d_g * r_g, digits balanced
+// in [-ceil(B/2), B/2), key coefficients balanced).  Eligible: exact path, gadget base <= 2^16 (int16
 // digits), every ciphertext prime 2^60 - d with d < 2^24 (ks32_crt reduces with reduce_near60),
 // 1024 <= n <= 16384; S <= 4.
 // One 31-bit basis for ks32: the fewest primes p == 1 mod 2n below pmax (largest first, all above
@@ -624,7 +629,7 @@ static int build_ks32_basis_impl(exacto_ctx* c, u64 pmax, u64 qmax, const Big& b
     if (!fixedS) {   // the lazy basis' limits come from the resident key (ks32_select_basis)
         Big one((u64)c->G);
         one.mul((u64)c->n);
-        one.mul(c->gbase / 2);
+        one.mul(digit_max(c->gbase));
         one.mul(qmax / 2);
         b->sum_max = std::max(1, sums_lifted(P, one, false));   // P > bound was checked above
         b->fpc_max = ps.size() <= 3 || narrow ? sums_lifted(P, one, true) : 0;   // ks32_crt's condition
@@ -743,8 +748,8 @@ static int build_ks32_basis(exacto_ctx* c, u64 pmax, u64 qmax, const Big& bound,
     return e;
 }
 
-// ks32.hip's auxiliary bases, bounding |sum_g d_g * r_g| <= G n floor(B/2) floor(q_max/2) (digits
-// balanced in [-B/2, B/2), key coefficients balanced).  Eligible: exact path, gadget base <= 2^16
+// ks32.hip's auxiliary bases, bounding |sum_g d_g * r_g| <= G n ceil(B/2) floor(q_max/2) (digits
+// balanced in [-ceil(B/2), B/2), key coefficients balanced).  Eligible: exact path, gadget base <= 2^16
 // (int16 digits), every ciphertext prime 2^60 - d with d < 2^24 (ks32_crt reduces with
 // reduce_near60), 1024 <= n <= 16384; S <= 4.
 //   primary: primes below 2^32 / 3, so that sums of three residues fit 32 bits and the MAC adds
@@ -763,7 +768,7 @@ static int setup_ks32(exacto_ctx* c) {
     }
     Big bound((u64)c->G);
     bound.mul((u64)c->n);
-    bound.mul(c->gbase / 2);
+    bound.mul(digit_max(c->gbase));
     bound.mul(qmax / 2);
     bound.mul(2);
     bound.add(1);
@@ -1510,7 +1515,7 @@ static int ks32_convert_key(exacto_ctx* c, const u64* key, size_t keys, uint32_t
 #define EXACTO_KN_NORM 1   // the narrow basis' digit-sum limit from the key's norms too (A/B build switch)
 #endif
 // The primary basis for the resident key: the lazy one (kz) when the key's own norms bound the key
-// switch, |u_{c,l}| <= (B/2) sum_g ||r_{g,c,l}||_1 with ||r||_1 <= (sum floor(|r_j|/2^20) + n) 2^20
+// switch, |u_{c,l}| <= ceil(B/2) sum_g ||r_{g,c,l}||_1 with ||r||_1 <= (sum floor(|r_j|/2^20) + n) 2^20
 // (ks32_key_norm_kernel), for every (c, l): prod p > 2 m bound for m = 1 (and sum_max = the largest
 // such m <= 64 for dBFV digit sums); otherwise the narrow one (kn), whose bound holds for any key.
 static int ks32_select_basis(exacto_ctx* c) {
@@ -1540,7 +1545,7 @@ static int ks32_select_basis(exacto_ctx* c) {
         }
         if (acc.cmp(worst) > 0) worst = acc;
     }
-    worst.mul(c->gbase / 2);
+    worst.mul(digit_max(c->gbase));
     // sums the lazy / the narrow basis lift for this key (its norms, not the analytic bound), by the
     // Garner and by the float-CRT lift
     const int sm = sums_lifted(c->kz.P, worst, false);
@@ -2357,16 +2362,16 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
     const Prime32* p32 = use_wide ? c->kw.d_p32 : c->d_p32;
     const Ks32Tables* kst = use_wide ? c->kw.d_kst : c->d_kst;
     const int mac_form = use_wide ? c->kw.mac_form : c->ks32_mac_form;
-    const bool wide = (u64)m * (c->gbase / 2) > 32767;   // digit sums beyond int16
+    const bool wide = (u64)m * digit_max(c->gbase) > 32767;   // digit sums beyond int16
     const size_t Bd = B * dout, Sn = (size_t)S * c->n;
     // HPS (u64_dbfv): with the products' c0 / c1 kept in the coefficient domain, relinearize is linear
     // mod q in the gadget digits and so are the per-limb sums and the NTT: limb k = NTT(sum c0) +
     // sum_g NTT(sum_p d_pg) (.) rlk_g.  The scale writes every product's signed digits (int8 when the
-    // base is at most 2^8), ks32_digit_sum adds them per output limb as int16 (|sum| <= m B / 2), and
+    // base is at most 2^8), ks32_digit_sum adds them per output limb as int16 (|sum| <= m ceil(B/2)), and
     // the forward NTTs and the MAC run once per output limb instead of once per product (u64_dbfv:
     // 8 instead of 36 products' worth of 10 forward NTTs and one MAC per dbfv_mul).
     const bool hps_sum = c->path == EXACTO_PATH_HPS && c->hps_sum_env && m > 0 && c->gbase <= 65536 &&
-                         (u64)m * (c->gbase / 2) <= 32767 && c->rlk_loaded && gu > 0 && c->n >= 1024 &&
+                         (u64)m * digit_max(c->gbase) <= 32767 && c->rlk_loaded && gu > 0 && c->n >= 1024 &&
                          !c->deferred_code;
     if (grouped) {
         // (the HPS sum multiplies with the key after the forward transform, once per output: never grouped)

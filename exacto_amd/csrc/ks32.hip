@@ -3,9 +3,9 @@
 // relinearize (reference src/bfv/keyswitch.rs:86-95) adds sum_g NTT_l(d_g) (.) rlk_{g,c,l} to the
 // scaled components, limb by limb.  By the negacyclic convolution theorem that is
 // NTT_l(sum_g d_g * r_{g,c,l} mod q_l) with r = INTT_l(rlk) the key in the coefficient domain.  The
-// digits d_g are small integers (|d| <= B/2) and the same for every limb, so the integer
+// digits d_g are small integers (|d| <= ceil(B/2)) and the same for every limb, so the integer
 // polynomial u_{c,l} = sum_g d_g * r_{g,c,l} (r balanced, |r| < q_l / 2) has coefficients below
-// G n (B/2) (q/2) in magnitude: for cfg3 below 2^90, for cfg5 below 2^84.  It is computed exactly
+// G n ceil(B/2) (q/2) in magnitude: for cfg3 below 2^90, for cfg5 below 2^84.  It is computed exactly
 // modulo S 31-bit primes p_s with prod p_s > 2 |u|max (S = 3 for every BASELINE config), then
 // lifted (Garner, centred) and reduced mod q_l.  Bit-identical with the limb-wise MAC by
 // construction; the work moves from G L 60-bit digit NTTs to G S 32-bit ones (no carry chains:

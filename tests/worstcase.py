@@ -1,13 +1,15 @@
 """Worst-case inputs for the two exactness bounds of the GPU path (test helper).
 
 1. The key switch over the integers (ks32): relinearize adds sum_g d_g * r_{g,c,l}
-   (keyswitch.rs:86-95), d_g the balanced gadget digits of c2 (|d| <= B/2) and r the key in the
-   coefficient domain, balanced (|r| <= q/2).  The library lifts that integer from a basis of 31-bit
-   primes p_s, exact while prod p_s > 2 m G n (B/2) (q/2) for m products whose digits are summed
-   first (dBFV).  `digit_inputs` makes EVERY coefficient of every product's c2 decompose into -B/2
-   in each of the low G' digits (all the digits a |value| < Q/2 can hold), and `aligned_key` makes
-   r = [-h, h, ..., h] (h = floor(q_l / 2)), so coefficient 0 of the key switch is
-   u_0 = m G' n (B/2) h: the bound with G' for G.
+   (keyswitch.rs:86-95), d_g the balanced gadget digits of c2 and r the key in the coefficient
+   domain, balanced (|r| <= q/2).  |d| <= hi = ceil(B/2): a positive remainder equal to floor(B/2)
+   becomes rem - B (keyswitch.rs:24-44), which for an odd base is -(B+1)/2.  The library lifts that
+   integer from a basis of 31-bit primes p_s, exact while prod p_s > 2 m G n hi (q/2) for m products
+   whose digits are summed first (dBFV, bfv_mul_sum).  `digit_inputs` makes EVERY coefficient of every
+   product's c2 decompose into -hi in each of the low G' digits (all the digits a |value| <= Q/2 can
+   hold), and `aligned_key` makes r = [-h, h, ..., h] (h = floor(q_l / 2)), so coefficient 0 of the
+   key switch is u_0 = m G' n hi h (less m n h where digit G' is the target's leading 1, odd bases
+   with G' < G): the bound with G' for G.
 2. psum (dBFV): an output limb's c0 / c1 are scaled once from the sum of its m products' tensors,
    exact while m (p n Q + 2) < P.  `tensor_inputs` makes every product's c1 tensor reach
    2 n floor(Q/2)^2 at coefficient 0 (a = (h, h, ..., h), b = (h, -h, ..., -h), h = floor(Q/2)),
@@ -36,14 +38,48 @@ def to_ntt(coeffs, moduli, n):
     return out
 
 
+def digit_max(base: int) -> int:
+    """The largest |balanced digit| of keyswitch.rs:24-44: ceil(B/2).  Remainders >= floor(B/2) become
+    rem - B, so a positive remainder floor(B/2) gives -(B - floor(B/2)); B/2 for an even base."""
+    return (base + 1) // 2
+
+
 def digit_target(Q: int, base: int, G: int) -> tuple[int, int]:
-    """(x, G'): x = -(B/2) (1 + B + ... + B^(G'-1)) with the most digits G' <= G such that |x| <= Q/2;
-    its balanced gadget digits (keyswitch.rs:24-44) are -B/2 in positions < G'."""
+    """(x, G'): the value with the most low digits G' <= G equal to -hi (hi = ceil(B/2)), |x| <= Q/2.
+    Even base: x = -(B/2) (1 + B + ... + B^(G'-1)), a negative value whose remainders -B/2 stand as
+    they are.  Odd base: only a positive remainder floor(B/2) gives -hi, so x is built backwards from
+    r = 1 by r <- r B - hi (remainder B - hi = floor(B/2), balanced to -hi, carry back to r); digit G'
+    is then that 1, or the dropped final carry when G' = G."""
+    if base % 2 == 0:
+        half = base // 2
+        gp = G
+        while gp > 0 and half * (base ** gp - 1) // (base - 1) > Q // 2:
+            gp -= 1
+        return -half * (base ** gp - 1) // (base - 1), gp
+    hi = digit_max(base)
+    x, gp = 1, 0
+    while gp < G and 0 < x * base - hi <= Q // 2:
+        x = x * base - hi
+        gp += 1
+    return (x, gp) if gp else (0, 0)
+
+
+def crafted_values(Q: int, base: int, G: int) -> list[int]:
+    """Canonical residues mod Q at the edges of keyswitch.rs:24-44: 0, 1, Q-1, floor(Q/2) and the
+    first negative value, +-(a remainder of exactly floor(B/2), alone and under a higher digit),
+    +-(B^k - 1) (a balancing carry rippling through k fields of B - 1), and the all -ceil(B/2) target."""
     half = base // 2
-    gp = G
-    while gp > 0 and half * (base ** gp - 1) // (base - 1) > Q // 2:
-        gp -= 1
-    return -half * (base ** gp - 1) // (base - 1), gp
+    vals = [0, 1, Q - 1, Q // 2, Q // 2 + 1]
+    for v in (half, half + base, half + 1, half * base + half):
+        vals += [v, -v]
+    kmax = 1
+    while base ** (kmax + 1) - 1 <= Q // 2:
+        kmax += 1
+    for k in sorted({1, 2, 3, kmax // 2, kmax - 1, kmax} - {0}):     # short, middling and the longest ripple
+        vals += [base ** k - 1, -(base ** k - 1)]
+    x, _ = digit_target(Q, base, G)
+    vals += [x, -x]
+    return [v % Q for v in vals if -(Q // 2) <= v < Q]
 
 
 def digit_inputs(moduli, plain, base, G, n):
@@ -63,7 +99,7 @@ def digit_inputs(moduli, plain, base, G, n):
         raise AssertionError("no coefficient rounds to the target")
     assert abs(v) <= Q // 2 and abs(c) <= Q // 2
     digits = gadget_decompose_coeff(x % Q, Q, base, G)
-    assert all(d == Q - base // 2 for d in digits[:gp]), "target digits are not -B/2"
+    assert all(d == Q - digit_max(base) for d in digits[:gp]), "target digits are not -ceil(B/2)"
     return [v] * n, [c] + [0] * (n - 1), x, gp
 
 
@@ -97,7 +133,7 @@ def digit_case_bfv(moduli, plain, base, G, n, seed=11):
 
 def digit_case_dbfv(moduli, plain, base, G, n, d, seed=12):
     """dbfv_mul inputs [1][d][2][L][n]: every limb of a is (random, a1), of b (random, b1), so every
-    product's c2 has digits -B/2 and a limb's m summed digits are -m B/2."""
+    product's c2 has digits -ceil(B/2) and a limb's m summed digits are -m ceil(B/2)."""
     rng = np.random.default_rng(seed)
     a1, b1, x, gp = digit_inputs(moduli, plain, base, G, n)
     A1, B1 = to_ntt(a1, moduli, n), to_ntt(b1, moduli, n)
@@ -121,11 +157,13 @@ def tensor_case_dbfv(moduli, n, d, G, seed=13):
 
 # ---------------------------------------------------------------- the bounds themselves, restated
 
-def ks32_basis(n, q_max, base, G, pmax, sums=1, maxs=4):
+def ks32_basis(n, q_max, base, G, pmax, sums=1, maxs=4, hi=None):
     """The library's 31-bit basis rule (context.hip build_ks32_basis): primes p == 1 mod 2n below
-    pmax and above 2^30, largest first, the fewest with prod p > 2 sums G n floor(B/2) floor(q/2)."""
+    pmax and above 2^30, largest first, the fewest with prod p > 2 sums G n hi floor(q/2), hi the
+    digit bound ceil(B/2) (`hi` given: the rule with that digit bound in its place)."""
     from oracle.modular import is_prime
-    bound = 2 * sums * G * n * (base // 2) * (q_max // 2) + 1
+    hi = digit_max(base) if hi is None else hi
+    bound = 2 * sums * G * n * hi * (q_max // 2) + 1
     ps, P = [], 1
     p = (pmax - 1) // (2 * n) * (2 * n) + 1
     while p > (1 << 30) and len(ps) < maxs:
@@ -136,6 +174,23 @@ def ks32_basis(n, q_max, base, G, pmax, sums=1, maxs=4):
                 return ps
         p -= 2 * n
     return None
+
+
+def ks32_sum_max(basis, n, q_max, base, G, hi=None, cap=64):
+    """context.hip sums_lifted for a basis of ks32_basis: the largest m <= cap with
+    prod p > 2 m G n hi floor(q/2) + 1, the sums the basis is taken to lift exactly."""
+    hi = digit_max(base) if hi is None else hi
+    one = G * n * hi * (q_max // 2)
+    P, m = math.prod(basis), 0
+    while m < cap and P > 2 * (m + 1) * one + 1:
+        m += 1
+    return m
+
+
+def int16_sums_wide(m: int, base: int, hi=None) -> bool:
+    """context.hip's `wide` test: m summed digits leave int16 (the sums are then kept as int32)."""
+    hi = digit_max(base) if hi is None else hi
+    return m * hi > 32767
 
 
 def lift_centred(u: int, primes) -> int:
