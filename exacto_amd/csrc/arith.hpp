@@ -45,7 +45,18 @@ struct PrimeConst {
     // inverse stage's two constants times R mod q (they cancel the products' R^-1)
     u64 qinv_neg;
     u64 n_inv_r, n_inv_rs, last_wr, last_wrs;
+    // The last inverse stage's two constants times the scale's CRT factor c of this prime (EXACTO_CRT_FOLD;
+    // the tensor's inverse then leaves x c instead of x, in the same range): c = p (Q / q_i)^-1 mod q_i
+    // (CrtTables::fpq_pz_w) for a ciphertext prime, fpc_pq[a] for an auxiliary one.  Zero where the
+    // float-sum CRT has no constants (HPS).
+    u64 fold_n, fold_ns, fold_w, fold_ws;
 };
+
+// Build-time A/B switch: 0 compiles the folded CRT factors out (the tensor and the scale then run
+// exactly as before them).
+#ifndef EXACTO_CRT_FOLD
+#define EXACTO_CRT_FOLD 1
+#endif
 
 // a b R^-1 mod q in [0, 2q) (R = 2^64) for a b < q 2^64 (a, b < q): Montgomery's REDC with
 // m = lo(a b) (-q^-1) mod 2^64; (a b + m q) / 2^64 = hi(a b) + hi(m q) + (lo(a b) != 0), since the

@@ -811,8 +811,7 @@ static int build_tables(exacto_ctx* c) {
         pc[t].tw_fwd = c->d_tw + (size_t)t * 2 * c->n;
         pc[t].tw_inv = c->d_tw + (size_t)t * 2 * c->n + c->n;
     }
-    HIP_TRY(dev_alloc((void**)&c->d_primes, NP * sizeof(PrimeConst)));
-    if (int e_ = upload(c, c->d_primes, pc.data(), NP * sizeof(PrimeConst))) return e_;
+    HIP_TRY(dev_alloc((void**)&c->d_primes, NP * sizeof(PrimeConst)));   // (uploaded below, with the CRT folds)
 
     // ---- CRT tables
     CrtTables& C = c->h_crt;
@@ -924,6 +923,7 @@ static int build_tables(exacto_ctx* c) {
             for (int k = 0; k < L; ++k)
                 if (k != i) qo = mulmod_h(qo, qv[k] % q, q);
             set_shoup(C.fpq_pz_w[i], C.fpq_pz_ws[i], mulmod_h(c->plain % q, invmod_h(qo, q), q), q);
+            set_shoup(C.fpq_qo_w[i], C.fpq_qo_ws[i], qo, q);
             C.fpq_inv0[i] = 1.0 / (double)q;
             C.fpq_inv1[i] = (double)(1ull << 30) / (double)q;
             for (int a = 0; a < K; ++a) {
@@ -931,7 +931,15 @@ static int build_tables(exacto_ctx* c) {
                 C.fpq_c[i][a] = mulmod_h((pa - qi) % pa, C.fpc_neg[a], pa);
             }
         }
+        // the last inverse stage's constants times the prime's CRT factor (PrimeConst::fold_*)
+        auto fold = [&](PrimeConst& P, u64 f) {
+            set_shoup(P.fold_n, P.fold_ns, mulmod_h(P.n_inv, f, P.q), P.q);
+            set_shoup(P.fold_w, P.fold_ws, mulmod_h(P.last_w, f, P.q), P.q);
+        };
+        for (int i = 0; i < L; ++i) fold(pc[i], C.fpq_pz_w[i]);
+        for (int a = 0; a < K; ++a) fold(pc[L + a], C.fpc_pq[a]);
     }
+    if (int e_ = upload(c, c->d_primes, pc.data(), NP * sizeof(PrimeConst))) return e_;
     {
         const u64 mx = *std::max_element(c->primes.begin(), c->primes.end());
         const u64 mn = *std::min_element(c->primes.begin(), c->primes.end());
@@ -1337,7 +1345,16 @@ static bool tensor_asm(const exacto_ctx* c) {
     return near60;
 }
 
-static int run_inv_tensor(exacto_ctx* c, const Operands& o, int cnt, bool p2only = false) {
+// The folded scale (EXACTO_CRT_FOLD): the tensor's last inverse stage multiplies by the constants the
+// float-sum scale would apply first, and the scale reads that form.  One decision for both launches of
+// run_mul: the asm special-prime tensor at n = 4096 with lazy outputs, and exact_scale_sp's FPQ form.
+static int crt_mode(const exacto_ctx* c);
+static bool scale_fold(const exacto_ctx* c) {
+    return c->path != EXACTO_PATH_HPS && crt_fold_tensor_ok(c->logn, tensor_asm(c), true) &&
+           exact_scale_fold_ok(c->L, c->K, crt_mode(c), c->fp_crt, c->fpq_lim);
+}
+
+static int run_inv_tensor(exacto_ctx* c, const Operands& o, int cnt, bool p2only = false, bool fold = false) {
     const int NP = c->L + c->K;
     bool lazy = true;
     const bool near60 = tensor_asm(c);
@@ -1365,7 +1382,7 @@ static int run_inv_tensor(exacto_ctx* c, const Operands& o, int cnt, bool p2only
     // the exact path's scale kernels take T in [0, 2q) (shoup products, 30-bit-limb dot products with
     // headroom); the HPS scale subtracts residues as canonical
     launch_inv_tensor(o, c->ws_extP, c->ws_T, cnt, c->logn, c->L, c->K, lazy, c->d_primes, c->stream, near60, p2only,
-                      qbits, c->tensor_share_npairs, near60 && c->path != EXACTO_PATH_HPS);
+                      qbits, c->tensor_share_npairs, near60 && c->path != EXACTO_PATH_HPS, fold);
     CHECK_LAUNCH();
     return 0;
 }
@@ -1678,7 +1695,9 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
             o.eb_off += s;
         }
         // 4+5. tensor product in every prime, fused into the inverse NTT of its components
-        if (int e = run_inv_tensor(c, o, cnt, ps.on)) return e;
+        // (psum's readers of T, fpq_acc, sum up to 15 canonical z_i: they keep the unfolded form)
+        const bool tfold = !ps.on && scale_fold(c);
+        if (int e = run_inv_tensor(c, o, cnt, ps.on, tfold)) return e;
         if (ps.on) {
             // the output limbs' c0 / c1 auxiliary residues, summed over their products, then inverse-
             // transformed: [ib][k][c][a][n] in extP (unused: the extensions are shared, steps 1-3 skipped)
@@ -1719,7 +1738,8 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
                                                   : c->ws_D16)
                                    : nullptr,
                                guse, cnt, n, c->d_crt, c->d_primes, L, K, crt_mode(c),
-                               c->stream, c->h_crt.gshift, ps.on, c->ks_defer && c->ks_defer8, c->fp_crt, c->fpq_lim);
+                               c->stream, c->h_crt.gshift, ps.on, c->ks_defer && c->ks_defer8, c->fp_crt, c->fpq_lim,
+                               tfold);
         CHECK_LAUNCH();
         }
         if (ps.on) {   // ... and their scale: the output limbs' c0 / c1, coefficient domain

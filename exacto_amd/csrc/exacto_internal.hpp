@@ -71,6 +71,9 @@ struct CrtTables {
     u64 fpq_pz_w[EXACTO_MAX_L], fpq_pz_ws[EXACTO_MAX_L];  // p (Q / q_i)^-1 mod q_i (Shoup)
     double fpq_inv0[EXACTO_MAX_L], fpq_inv1[EXACTO_MAX_L]; // fl(1 / q_i), fl(2^30 / q_i)
     u64 fpq_c[EXACTO_MAX_L][EXACTO_MAX_K];                 // (p_a - q_i^-1 mod p_a) Pi_a
+    // EXACTO_CRT_FOLD: the tensor's inverse leaves z_i itself (PrimeConst::fold_*); (Q / q_i) mod q_i takes a
+    // lane in the band back to u_i = p T_i = z_i (Q / q_i) mod q_i (fpc_y_garner FOLD)
+    u64 fpq_qo_w[EXACTO_MAX_L], fpq_qo_ws[EXACTO_MAX_L];
     int near;       // max prime < 2 * min prime: residues move between primes by one conditional subtraction
     int fast;       // near and every prime < 2^60: lazy CRT kernels (unreduced Shoup sums)
     int special;    // fast and every prime is 2^60 - d, d < 2^24: reduce_near60 instead of reduce64
@@ -190,7 +193,10 @@ void launch_drop_prime(const u64* in, u64* out, long rows, int l, bool round, co
 // psum; asm_inv and n = 4096 / 8192 only)
 void launch_inv_tensor(const Operands& op, const u64* extP, u64* T, int items, int logn, int L, int K, bool lazy,
                        const PrimeConst* primes, hipStream_t s, bool asm_inv = false, bool p2only = false,
-                       int qbits = 64, int share_np = 0, bool lazy_out = false);
+                       int qbits = 64, int share_np = 0, bool lazy_out = false, bool fold = false);
+// fold: T holds the folded scale's form (ntt_inv_tensor_kernel FOLD); the caller asked crt_fold_tensor_ok and
+// hands the same decision to launch_exact_scale
+bool crt_fold_tensor_ok(int logn, bool asm_inv, bool lazy_out);
 // lazy_out (asm_inv only): T's residues in [0, 2q) instead of canonical -- for the exact path's
 // scale kernels (shoup products and 30-bit-limb dot products), never for HPS
 // Decryption (bfv/encrypt.rs:111-178, dbfv/decrypt.rs:20-79), kernels.hip.
@@ -222,7 +228,9 @@ bool exact_scale_sp_ok(int L, int K, int mode);
 void launch_exact_scale(const u64* T, u64* R, long r_stride, int ncomp_r, u64* D, int16_t* D16, int guse,
                         int items, int n, const CrtTables* ct, const PrimeConst* primes, int L,
                         int K, int mode, hipStream_t s, int gshift = -1, bool c2only = false,
-                        bool digits8 = false, bool fpc = false, double fpq_lim = 0.0);
+                        bool digits8 = false, bool fpc = false, double fpq_lim = 0.0, bool fold = false);
+// fold: T is the folding tensor's (launch_inv_tensor fold); the caller asks exact_scale_fold_ok first
+bool exact_scale_fold_ok(int L, int K, int mode, bool fpc, double fpq_lim);
 // fpq_lim > 0 (with fpc): s = [p T]_Q centred by the float sum (fpq_y) wherever |f - round(f)| <= fpq_lim,
 // Garner over Q elsewhere (0.5 - 2^-40: exact; smaller values only send more coefficients to Garner)
 // D: digits as residues mod q [item][g][n]; D16 (instead): signed int16 (d8: int8) digits [item][g][n].

@@ -519,13 +519,18 @@ __device__ __forceinline__ void fpc_lift(const u64 (&y)[LT + 1], u64 (&res)[EXAC
 // (mixed-radix digits v, their comparison with floor(Q/2)), then
 //   y_a = T_a fpc_pq[a] + sum_k v_k fpc_qpq[k][a] + negs Pi_a   (mod p_a, in [0, p_a)).
 // `carry` (psum: the products' running sum, < p_a) is added to each y_a; T_a's term only when ta is set.
-template <int LT, bool TA>
+// FOLD (the tensor wrote z_i and T_a fpc_pq[a], fpq_y): u_i = z_i (Q / q_i) mod q_i, one Shoup product as
+// before, and T_a's term is added, not multiplied.
+template <int LT, bool TA, bool FOLD = false>
 __device__ __forceinline__ void fpc_y_garner(const u64* __restrict__ Tin, int n, u64 (&y)[LT + 1],
                                              const CrtTables* __restrict__ C, const PrimeConst* __restrict__ primes) {
     constexpr int L = LT, K = LT + 1;
+    static_assert(!FOLD || TA, "the folded tensor feeds the scale alone");
     u64 u[EXACTO_MAX_L], v[EXACTO_MAX_L];
 #pragma unroll
-    for (int i = 0; i < L; ++i) u[i] = shoup_mul(Tin[(long)i * n], C->pmod_w[i], C->pmod_ws[i], primes[i].q);
+    for (int i = 0; i < L; ++i)
+        u[i] = FOLD ? shoup_mul(Tin[(long)i * n], C->fpq_qo_w[i], C->fpq_qo_ws[i], primes[i].q)
+                    : shoup_mul(Tin[(long)i * n], C->pmod_w[i], C->pmod_ws[i], primes[i].q);
     garner_q_fast<LT>(v, u, L, C, primes);
     const bool negs = mr_greater<EXACTO_MAX_L>(v, C->halfQ_mr, L);
     uint32_t v0[L], v1[L];
@@ -538,7 +543,9 @@ __device__ __forceinline__ void fpc_y_garner(const u64* __restrict__ Tin, int n,
     for (int a = 0; a < K; ++a) {
         // y[a] (TA: unused on entry; else the carry < p_a): a0's constant < 2^61, inside dot30_fold's budget
         Dot30 A{(TA ? 0ull : y[a]) + (negs ? C->fpc_neg[a] : 0ull), 0, 0};
-        if constexpr (TA) {
+        if constexpr (TA && FOLD) {
+            A.a0 += Tin[(long)(L + a) * n];   // T_a fpc_pq[a] in [0, 2q): a0's constants < 2^60 + 2^61
+        } else if constexpr (TA) {
             const u64 ta = Tin[(long)(L + a) * n];   // [0, 2q) (the tensor's lazy last stage)
             dot30_mac(A, (uint32_t)ta & M30, (uint32_t)(ta >> 30), C->fpc_pq[a]);
         }
@@ -556,15 +563,23 @@ __device__ __forceinline__ void fpc_y_garner(const u64* __restrict__ Tin, int n,
 // (s Q^-1 = sum_i z_i q_i^-1 - beta).  Elsewhere (s within 2^-40 Q of +-Q/2; about 2^-39 of uniform
 // coefficients) the lane takes fpc_y_garner.  Replaces Garner over Q's L (L - 1) / 2 Shoup products and
 // the mixed-radix comparison with 2 L conversions and fused multiply-adds.
-template <int LT, bool TA>
+// FOLD: the tensor's last inverse stage has already multiplied by the constants (ntt_inv_tensor_kernel
+// FOLD), so Tin holds z_i and T_a fpc_pq[a], both in [0, 2q): z_i's product and T_a's dot term go.  A z_i
+// of q_i more raises f and beta by exactly one (beta <= 2 L) and changes no y_a: q_i fpq_c[i][a] == -Pi_a.
+// The halves of z_i stay exact doubles (z1 < 2^31), f < 2 L keeps the float error below 2^-45, and the
+// dot stays inside its 64-bit columns for L <= 5: a0 < 2^61 + L 2^60 + 2^34, a1 < 3 L 2^60 + 2^34
+// (z1 c0 < 2^61), a2 < 2 L 2^60, and dot30_fold's five terms sum below (L + 4.2) 2^60.
+template <int LT, bool TA, bool FOLD = false>
 __device__ __forceinline__ void fpq_y(const u64* __restrict__ Tin, int n, u64 (&y)[LT + 1], const CrtTables* __restrict__ C,
                                       const PrimeConst* __restrict__ primes, double lim) {
     constexpr int L = LT, K = LT + 1;
+    static_assert(!FOLD || (TA && LT <= 5), "folded form: the scale's own tensor, L <= 5 (dot budget)");
     uint32_t z0[L], z1[L];
     double f = 0.0;
 #pragma unroll
     for (int i = 0; i < L; ++i) {
-        const u64 z = shoup_mul_red(Tin[(long)i * n], C->fpq_pz_w[i], C->fpq_pz_ws[i], primes[i].q);
+        const u64 z = FOLD ? Tin[(long)i * n]
+                           : shoup_mul_red(Tin[(long)i * n], C->fpq_pz_w[i], C->fpq_pz_ws[i], primes[i].q);
         z0[i] = (uint32_t)z & M30;
         z1[i] = (uint32_t)(z >> 30);
         f = fma((double)z0[i], C->fpq_inv0[i], f);
@@ -572,12 +587,12 @@ __device__ __forceinline__ void fpq_y(const u64* __restrict__ Tin, int n, u64 (&
     }
     const double b = __builtin_rint(f);
     if (__builtin_fabs(f - b) <= lim) {
-        const uint32_t beta = (uint32_t)b;   // 0 .. L
+        const uint32_t beta = (uint32_t)b;   // 0 .. L (FOLD: 2 L)
 #pragma unroll
         for (int a = 0; a < K; ++a) {
-            Dot30 A{TA ? 0ull : y[a], 0, 0};
-            dot30_mac(A, beta, 0, C->fpc_neg[a]);     // < 2^33 in a0 and a1: not a full term
-            if constexpr (TA) {
+            Dot30 A{TA ? (FOLD ? Tin[(long)(L + a) * n] : 0ull) : y[a], 0, 0};
+            dot30_mac(A, beta, 0, C->fpc_neg[a]);     // < 2^34 in a0 and a1: not a full term
+            if constexpr (TA && !FOLD) {
                 const u64 ta = Tin[(long)(L + a) * n];
                 dot30_mac(A, (uint32_t)ta & M30, (uint32_t)(ta >> 30), C->fpc_pq[a]);
             }
@@ -586,7 +601,7 @@ __device__ __forceinline__ void fpq_y(const u64* __restrict__ Tin, int n, u64 (&
             y[a] = dot30_fold(A, primes[L + a].q);
         }
     } else {
-        fpc_y_garner<LT, TA>(Tin, n, y, C, primes);
+        fpc_y_garner<LT, TA, FOLD>(Tin, n, y, C, primes);
     }
 }
 
@@ -656,8 +671,8 @@ __device__ __forceinline__ void fpq_flush(u64 (&Z)[LT], uint32_t& bs, u64 (&carr
 //   r_a = T_a (p Q^-1) + sum_k v_k (p_a - qpq_k,a) + negs        mod p_a   (then Garner over P)
 //   res_i = sum_a w_a (p_0 .. p_{a-1}) + negr (q_i - P mod q_i)    mod q_i
 // (FPC: y_a = r_a Pi_a by the same dots with folded constants, then fpc_lift), and int16 gadget
-// digits by gadget_digits16_sp.
-template <int LT, int DIG, bool FPC, bool FPQ = false>
+// digits by gadget_digits16_sp.  FOLD (FPQ only): T as the folding tensor kernels leave it (fpq_y).
+template <int LT, int DIG, bool FPC, bool FPQ = false, bool FOLD = false>
 __global__ void __launch_bounds__(TPB)
 exact_scale_sp_kernel(const u64* __restrict__ T, u64* __restrict__ R, long r_stride, int ncomp_r,
                       u64* __restrict__ D, int16_t* __restrict__ D16, int guse, int n,
@@ -672,7 +687,7 @@ exact_scale_sp_kernel(const u64* __restrict__ T, u64* __restrict__ R, long r_str
     if constexpr (FPQ) {
         static_assert(FPC, "FPQ feeds the float lift from P");
         u64 y[K];
-        fpq_y<LT, true>(Tin, n, y, C, primes, fpq_lim);
+        fpq_y<LT, true, FOLD>(Tin, n, y, C, primes, fpq_lim);
         fpc_lift<LT>(y, res, C, primes);
     } else {
     u64 u[EXACTO_MAX_L], v[EXACTO_MAX_L];
@@ -893,19 +908,31 @@ bool launch_psum_scale(const u64* T, const u64* Tsum, u64* out, int items_b, int
 
 bool exact_scale_sp_ok(int L, int K, int mode) { return mode == 3 && K == L + 1 && L >= 1 && L <= 6 && use_dot30(); }
 
+// launch_exact_scale runs exact_scale_sp_kernel's FPQ form and that form reads a folded T (fpq_y: L <= 5)
+bool exact_scale_fold_ok(int L, int K, int mode, bool fpc, double fpq_lim) {
+    return EXACTO_CRT_FOLD && exact_scale_sp_ok(L, K, mode) && L <= 5 && fpc && fpq_lim > 0.0;
+}
+
 void launch_exact_scale(const u64* T, u64* R, long r_stride, int ncomp_r, u64* D, int16_t* D16, int guse,
                         int items, int n, const CrtTables* ct, const PrimeConst* primes, int L,
                         int K, int mode, hipStream_t s, int gshift, bool c2only, bool digits8, bool fpc,
-                        double fpq_lim) {
+                        double fpq_lim, bool fold) {
     const long blocks = (long)items * (c2only ? 1 : 3) * blocks_per_row(n);
     if (blocks == 0) return;
     if (mode == 3 && K == L + 1 && L >= 1 && L <= 6 && use_dot30()) {
         // digit code: 0 none, 1 int16 fields of the magnitude (base 2^sh, sh | 32), 2 gadget_digits
         const int dig = (D16 == nullptr && D == nullptr) || guse <= 0 ? 0
                         : (D16 != nullptr && gshift > 0 && 32 % gshift == 0) ? (digits8 && gshift <= 8 ? 3 : 1) : 2;
+        // the folded T (the caller asked exact_scale_fold_ok, and crt_fold_tensor_ok of the tensor launch);
+        // L = 6 and an EXACTO_CRT_FOLD=0 build name the unfolded instance twice
+        const bool folded = fold && exact_scale_fold_ok(L, K, mode, fpc, fpq_lim);
 #define SCALE30_(LT, DG)                                                                                        \
     do {                                                                                                        \
-        if (fpc && fpq_lim > 0.0)                                                                               \
+        if (folded)                                                                                             \
+            EXACTO_LAUNCH((exact_scale_sp_kernel<LT, DG, true, true, (EXACTO_CRT_FOLD != 0 && LT <= 5)>),       \
+                          dim3(blocks), dim3(TPB), 0, s, T, R, r_stride, ncomp_r, D, D16, guse, n, ct, primes,  \
+                          c2only ? 1 : 0, fpq_lim);                                                             \
+        else if (fpc && fpq_lim > 0.0)                                                                          \
             EXACTO_LAUNCH((exact_scale_sp_kernel<LT, DG, true, true>), dim3(blocks), dim3(TPB), 0, s, T, R,     \
                           r_stride, ncomp_r, D, D16, guse, n, ct, primes, c2only ? 1 : 0, fpq_lim);             \
         else if (fpc) EXACTO_LAUNCH((exact_scale_sp_kernel<LT, DG, true>), dim3(blocks), dim3(TPB), 0, s, T, R, \

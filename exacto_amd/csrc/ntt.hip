@@ -287,6 +287,18 @@ ntt_fwd_kernel(NttBatch nb, const PrimeConst* __restrict__ primes) {
 // Same convention, same LDS exchanges and same output layout as ntt_fwd_kernel.
 #include "ntt_asm.inc"
 
+// make_asmk_inv (ntt_asm.inc) with the last stage's constants times the scale's CRT factor of the prime
+// (PrimeConst::fold_*): the tensor's inverse leaves x c, and the float-sum scale skips its own product by
+// c.  The generated rounds are the same; only the constants they are handed change.
+__device__ __forceinline__ AsmK make_asmk_inv_fold(const PrimeConst& P) {
+    AsmK K = make_asmk(P.q);
+    K.nil = (uint32_t)P.fold_n; K.nih = (uint32_t)(P.fold_n >> 32);
+    K.nsl = (uint32_t)P.fold_ns; K.nsh = (uint32_t)(P.fold_ns >> 32);
+    K.lwl = (uint32_t)P.fold_w; K.lwh = (uint32_t)(P.fold_w >> 32);
+    K.lsl = (uint32_t)P.fold_ws; K.lsh = (uint32_t)(P.fold_ws >> 32);
+    return K;
+}
+
 // The swizzle is linear over GF(2) and elem_index<LO>(tid, k) = A(tid) ^ (k << LO) with disjoint
 // bits, so every exchange address is one per-thread base XOR a compile-time constant: one VALU
 // per access instead of recomputing the swizzle of each index.
@@ -922,7 +934,10 @@ __device__ __forceinline__ void tensor_block(long b, long total, int per, int L,
 // GEN (n = 4096 / 8192, every prime below 2^60 but not all 2^60 - d: HPS): lazy Barrett products,
 // then the generated generic-prime inverse rounds (InvRoundGenAsm) instead of the C++ ones.
 // LZO (ASM only): outputs in [0, 2q), as ntt_inv_tensor_pin_kernel
-template <int LOGN, bool LAZY, bool ASM = false, int PROBE = 0, bool GEN = false, int QB = 60, bool LZO = false>
+// FOLD (ASM only): the last stage's constants carry the prime's scale factor (PrimeConst::fold_*), so
+// T holds z_i = T_i p (Q / q_i)^-1 mod q_i and T_a fpc_pq[a] mod p_a, in the range T_i and T_a had
+template <int LOGN, bool LAZY, bool ASM = false, int PROBE = 0, bool GEN = false, int QB = 60, bool LZO = false,
+          bool FOLD = false>
 __global__ void __launch_bounds__((1 << LOGN) / 16 < 64 ? 64 : (1 << LOGN) / 16)
 __attribute__((amdgpu_waves_per_eu(3)))  // the ASM form otherwise takes 184 VGPRs (2 waves/SIMD)
 ntt_inv_tensor_kernel(Operands op, const u64* __restrict__ extP, u64* __restrict__ Tout, int L, int K,
@@ -1021,7 +1036,8 @@ ntt_inv_tensor_kernel(Operands op, const u64* __restrict__ extP, u64* __restrict
     if constexpr (PROBE == 2) {
         // no transform: the products are stored as they are
     } else if constexpr (ASM || GEN) {
-        const AsmK AK = GEN ? make_asmk_inv_mont(P) : make_asmk_inv(P);
+        static_assert(!FOLD || (ASM && !GEN), "the folded constants exist for the special-prime rounds");
+        const AsmK AK = GEN ? make_asmk_inv_mont(P) : FOLD ? make_asmk_inv_fold(P) : make_asmk_inv(P);
         inv_rounds_asm<LOGN, 0, GEN, QB, LZO && ASM && !GEN>(x, lds, tid, tw_table(P.tw_inv), AK);
     } else {
         inv_rounds<LOGN, 0, LAZY>(x, lds, tid, tw_table(P.tw_inv), P);
@@ -1038,8 +1054,8 @@ ntt_inv_tensor_kernel(Operands op, const u64* __restrict__ extP, u64* __restrict
 // PIN_INV_ROUNDS -- one set of value registers, four waves per SIMD (n = 8192: two 8-wave
 // workgroups per CU).  Same blocks, remap and p2only as ntt_inv_tensor_kernel.
 // LZO: outputs in [0, 2q) (the exact path's scale kernels take them; never for HPS, whose scale
-// subtracts residues as canonical)
-template <int LOGN, bool LZO = false>
+// subtracts residues as canonical); FOLD: as ntt_inv_tensor_kernel
+template <int LOGN, bool LZO = false, bool FOLD = false>
 __global__ void __launch_bounds__((1 << LOGN) / 16) __attribute__((amdgpu_waves_per_eu(4)))
 ntt_inv_tensor_pin_kernel(Operands op, const u64* __restrict__ extP, u64* __restrict__ Tout, int L, int K,
                           const PrimeConst* __restrict__ primes, int remap, int p2only, int share_np) {
@@ -1103,7 +1119,9 @@ ntt_inv_tensor_pin_kernel(Operands op, const u64* __restrict__ extP, u64* __rest
 #undef PIN_T2
     }
 #undef LDE
-    if constexpr (LZO) {
+    if constexpr (LZO && FOLD) {
+        PIN_INV_ROUNDS(LOGN, lds, tid, tw_table(P.tw_inv), make_asmk_inv_fold(P), _LZ)
+    } else if constexpr (LZO) {
         PIN_INV_ROUNDS(LOGN, lds, tid, tw_table(P.tw_inv), make_asmk_inv(P), _LZ)
     } else {
         PIN_INV_ROUNDS(LOGN, lds, tid, tw_table(P.tw_inv), make_asmk_inv(P), )
@@ -1532,13 +1550,22 @@ static bool gen_small(int qbits) {
 template <int LOGN>
 static void launch_it(const Operands& op, const u64* extP, u64* T, long blocks, int L, int K, bool lazy,
                       const PrimeConst* primes, hipStream_t s, bool asm_inv = false, int p2only = 0, int qbits = 64,
-                      int np = 0, bool lzo = false) {
+                      int np = 0, bool lzo = false, bool fold = false) {
     constexpr int threads = (1 << LOGN) / 16;
     // EXACTO_XCD_REMAP=0: plain block order (A/B switch)
     static const int remap = [] { const char* e = std::getenv("EXACTO_XCD_REMAP"); return (e && e[0] == '0') ? 0 : 1; }();
     if constexpr (LOGN == 12 || LOGN == 13) {
         if (asm_inv && tensor_pin_at(LOGN)) {
             const long b2 = p2only ? blocks / (3 * (L + K)) * (3 * L + K) : blocks;
+#if EXACTO_CRT_FOLD
+            if constexpr (LOGN == 12) {
+                if (lzo && fold) {
+                    EXACTO_LAUNCH((ntt_inv_tensor_pin_kernel<LOGN, true, true>), dim3(b2), dim3(threads), 0, s, op,
+                                       extP, T, L, K, primes, remap, p2only, np);
+                    return;
+                }
+            }
+#endif
             if (lzo)
                 EXACTO_LAUNCH((ntt_inv_tensor_pin_kernel<LOGN, true>), dim3(b2), dim3(threads), 0, s, op, extP, T,
                                    L, K, primes, remap, p2only, np);
@@ -1549,6 +1576,15 @@ static void launch_it(const Operands& op, const u64* extP, u64* T, long blocks, 
         }
         if (asm_inv) {
             const long b2 = p2only ? blocks / (3 * (L + K)) * (3 * L + K) : blocks;
+#if EXACTO_CRT_FOLD
+            if constexpr (LOGN == 12) {
+                if (lzo && fold) {
+                    EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, true, 0, false, 60, true, true>), dim3(b2),
+                                       dim3(threads), 0, s, op, extP, T, L, K, primes, remap, p2only, np);
+                    return;
+                }
+            }
+#endif
             if (lzo)
                 EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, true, 0, false, 60, true>), dim3(b2),
                                    dim3(threads), 0, s, op, extP, T, L, K, primes, remap, p2only, np);
@@ -1577,9 +1613,15 @@ static void launch_it(const Operands& op, const u64* extP, u64* T, long blocks, 
                            K, primes, remap);
 }
 
+// The tensor kernels that take the folded last-stage constants: n = 4096, special primes with the
+// generated products (an EXACTO_MUL_ASM=0 build keeps T as it was), outputs in [0, 2q).
+bool crt_fold_tensor_ok(int logn, bool asm_inv, bool lazy_out) {
+    return EXACTO_CRT_FOLD && EXACTO_MUL_ASM && logn == 12 && asm_inv && lazy_out;
+}
+
 void launch_inv_tensor(const Operands& op, const u64* extP, u64* T, int items, int logn, int L, int K, bool lazy,
                        const PrimeConst* primes, hipStream_t s, bool asm_inv, bool p2only, int qbits, int share_np,
-                       bool lazy_out) {
+                       bool lazy_out, bool fold) {
     // prime-major block order needs whole dBFV items in the launch (tensor_block)
     // (measured: cfg5, 36 products per item, tensor 270 -> 261 us; cfg4's 3 products per item and
     // u64_dbfv within noise: applied from 8 products per item; round 6 again at cfg4:
@@ -1601,7 +1643,10 @@ void launch_inv_tensor(const Operands& op, const u64* extP, u64* T, int items, i
         case 9: launch_it<9>(op, extP, T, blocks, L, K, lazy, primes, s); break;
         case 10: launch_it<10>(op, extP, T, blocks, L, K, lazy, primes, s, false, 0, qbits, share_np); break;
         case 11: launch_it<11>(op, extP, T, blocks, L, K, lazy, primes, s); break;
-        case 12: launch_it<12>(op, extP, T, blocks, L, K, lazy, primes, s, asm_inv, 0, qbits, share_np, lazy_out); break;
+        case 12:
+            launch_it<12>(op, extP, T, blocks, L, K, lazy, primes, s, asm_inv, 0, qbits, share_np, lazy_out,
+                          fold && crt_fold_tensor_ok(logn, asm_inv, lazy_out));
+            break;
         case 13: launch_it<13>(op, extP, T, blocks, L, K, lazy, primes, s, asm_inv, 0, qbits, share_np, lazy_out); break;
         case 14: launch_it<14>(op, extP, T, blocks, L, K, lazy, primes, s); break;
         default: break;
