@@ -396,7 +396,10 @@ static void octx_free(octx_t* c) {
 }
 
 /* ------------------------------------------------------------------ generic exact path (eval.rs:113-147) */
-static void mul_generic(const octx_t* c, const u64* ct1, const u64* ct2, u64* r /* [3][L][n] coeff */) {
+/* inner > 1: the schoolbook of this one product on `inner` threads, each owning whole output coefficients
+ * (the same integer products and sums in another order: bit-identical); for batches smaller than the
+ * thread count. */
+static void mul_generic(const octx_t* c, const u64* ct1, const u64* ct2, u64* r /* [3][L][n] coeff */, int inner) {
     const int n = c->n, L = c->L;
     const int W = 2 * L + 2;
     /* 1. centred lifts of c0, c1, d0, d1: sign + L-word magnitude */
@@ -418,6 +421,28 @@ static void mul_generic(const octx_t* c, const u64* ct1, const u64* ct2, u64* r 
     mw_t* T = (mw_t*)calloc((size_t)3 * n, sizeof(mw_t));
     const int pa[4] = {0, 0, 1, 1}, pb[4] = {2, 3, 2, 3}, dst[4] = {0, 1, 1, 2};
     u64 prod[2 * MAXL];
+#ifdef _OPENMP
+    if (inner > 1) {
+#pragma omp parallel for num_threads(inner) schedule(static)
+        for (int idx = 0; idx < n; ++idx) {
+            u64 pr[2 * MAXL];
+            for (int t = 0; t < 4; ++t) {
+                const u64* A = mag + (size_t)pa[t] * n * L;
+                const u64* Bm = mag + (size_t)pb[t] * n * L;
+                const int* sa = sg + pa[t] * n;
+                const int* sb = sg + pb[t] * n;
+                mw_t* o = T + (size_t)dst[t] * n + idx;
+                for (int i = 0; i < n; ++i) {
+                    int j = idx - i, neg = sa[i];
+                    if (j < 0) { j += n; neg ^= 1; }   /* i + j = idx + n: X^n = -1 */
+                    neg ^= sb[j];
+                    mag_mul(pr, A + (size_t)i * L, Bm + (size_t)j * L, L);
+                    mw_add_mag(o, pr, 2 * L, W, neg);
+                }
+            }
+        }
+    } else
+#endif
     for (int t = 0; t < 4; ++t) {
         const u64* A = mag + (size_t)pa[t] * n * L;
         const u64* Bm = mag + (size_t)pb[t] * n * L;
@@ -547,11 +572,11 @@ static void mul_hps(const octx_t* c, const u64* ct1, const u64* ct2, u64* r /* [
 /* One product (eval.rs:73-108 + keyswitch.rs:59-101): ct1, ct2 = [2][L][n] -> o = [2][L][n] (relin)
  * or [3][L][n], NTT domain. */
 static void bfv_mul_one(const octx_t* c, int hps, const u64* ct1, const u64* ct2, const u64* rlk, int guse,
-                        int relin, u64* o) {
+                        int relin, u64* o, int inner) {
     const int n = c->n, L = c->L, G = c->G;
     u64* r = (u64*)malloc(sizeof(u64) * 3 * L * n);
     if (hps) mul_hps(c, ct1, ct2, r);
-    else mul_generic(c, ct1, ct2, r);
+    else mul_generic(c, ct1, ct2, r, inner);
     if (!relin) {
         memcpy(o, r, sizeof(u64) * 3 * L * n);
         for (int k = 0; k < 3; ++k)
@@ -603,10 +628,17 @@ int oracle_bfv_mul(int n, int L, const u64* q, int K, const u64* aux, u64 plain,
     const int guse = G < nkeys ? G : nkeys;
 #ifdef _OPENMP
     if (threads > 0) omp_set_num_threads(threads);
+    if (!hps && threads > B) {   /* fewer products than threads: one after the other, each on all threads */
+        for (int b = 0; b < B; ++b)
+            bfv_mul_one(&c, hps, ct1 + b * ctw, ct2 + b * ctw, rlk, guse, relin,
+                        out + (size_t)b * (relin ? 2 : 3) * L * n, threads);
+        octx_free(&c);
+        return 0;
+    }
 #pragma omp parallel for schedule(dynamic, 1)
 #endif
     for (int b = 0; b < B; ++b)
-        bfv_mul_one(&c, hps, ct1 + b * ctw, ct2 + b * ctw, rlk, guse, relin, out + (size_t)b * (relin ? 2 : 3) * L * n);
+        bfv_mul_one(&c, hps, ct1 + b * ctw, ct2 + b * ctw, rlk, guse, relin, out + (size_t)b * (relin ? 2 : 3) * L * n, 1);
     octx_free(&c);
     return 0;
 }
@@ -638,7 +670,7 @@ int oracle_dbfv_mul(int n, int L, const u64* q, int K, const u64* aux, u64 plain
         const long item = w / (d * d);
         const int i = (int)(w % (d * d)) / d, j = (int)(w % d);
         bfv_mul_one(&c, hps, a + ((size_t)item * d + i) * ctw, b + ((size_t)item * d + j) * ctw, rlk, guse, 1,
-                    prod + (size_t)w * ctw);
+                    prod + (size_t)w * ctw, 1);
     }
     u64* limbs = (u64*)calloc((size_t)R * ctw, sizeof(u64));
     for (int item = 0; item < B; ++item) {

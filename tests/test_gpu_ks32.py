@@ -14,11 +14,13 @@ import os
 import numpy as np
 import pytest
 
-from oracle import bfv as obfv, params as P
+import automorphism_ref
+from oracle import bfv as obfv, cref, params as P
 from exacto_amd._ffi import HipContext
 from bridge import ct_to_np, np_to_ct, np_to_rlk, uniform_residues
 
 pytestmark = pytest.mark.gpu
+THREADS = min(16, os.cpu_count() or 1)     # oracle/c: one product on all threads where the batch is smaller
 
 
 def _ctx(prm, ks32: bool, chunk=0):
@@ -72,6 +74,10 @@ def test_ks32_matches_limbwise_mac(gpu_available, n, which, B, keys, chunk):
         ctx.load_relin_key(rlk)
         outs.append(ctx.bfv_mul_and_relin(ct1, ct2))
     assert np.array_equal(outs[0], outs[1])
+    # every row at every size against oracle/c (the two contexts share the transforms, the tensor, the scale
+    # and the digits: their agreement alone says nothing about those)
+    assert cref.available(), "oracle/c/liboracle.so is not built: run build() of __graft_entry__.py"
+    assert np.array_equal(outs[0], cref.bfv_mul(prm, ct1, ct2, rlk, relin=True, threads=THREADS))
     if n <= 1024:
         want = ct_to_np(obfv.bfv_mul_and_relin(np_to_ct(ct1[0], prm), np_to_ct(ct2[0], prm), np_to_rlk(rlk, prm)))
         assert np.array_equal(outs[0][0], want)
@@ -114,6 +120,8 @@ def test_ks32_automorphism_matches_limbwise(gpu_available, n, which, B, keys, ch
         gk = uniform_residues(rng, (keys or prm.gadget_digits, 2), q, n)
         got, want = (c.bfv_apply_automorphism(ct, element, gk) for c in ctxs)
         assert np.array_equal(got, want), (n, element)
+        # every row at every size: the oracle's steps with oracle/c's transforms (tests/automorphism_ref.py)
+        assert np.array_equal(got, automorphism_ref.apply_automorphism(prm, ct, element, gk, threads=THREADS)), (n, element)
         if n <= 1024:
             keyset = obfv.GaloisKey(np_to_rlk(gk, prm).keys, element, prm)
             assert np.array_equal(got[0], ct_to_np(obfv.bfv_apply_automorphism(np_to_ct(ct[0], prm), keyset)))
