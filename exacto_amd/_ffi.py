@@ -83,6 +83,14 @@ _SIGS = [
     ("exacto_bfv_mul_and_relin", [_P, _P, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_mul_and_relin_dev", [_P, _P, _P, _P, _SZ], C.c_int),
     ("exacto_gadget_decompose_dev", [_P, _P, _P, _SZ, _SZ], C.c_int),
+    ("exacto_bfv_square_no_relin", [_P, _P, _SZ, _P, _SZ], C.c_int),
+    ("exacto_bfv_square_no_relin_dev", [_P, _P, _SZ, _P, _SZ], C.c_int),
+    ("exacto_bfv_square_and_relin", [_P, _P, _P, _SZ], C.c_int),
+    ("exacto_bfv_square_and_relin_dev", [_P, _P, _P, _SZ], C.c_int),
+    ("exacto_ctx_set_square_hook", [_P, C.c_int], C.c_int),
+    ("exacto_dbfv_square", [_P, _SZ, _U64, _U64, _P, _P, _SZ, _P, _P], C.c_int),
+    ("exacto_dbfv_square_dev", [_P, _SZ, _U64, _U64, _P, _P, _SZ, _P, _P], C.c_int),
+    ("exacto_dbfv_mul_plan", [_SZ, _U64, _U64, C.c_int, _P, _SZ, _P, _P, _P, _SZ, _P], C.c_int),
     ("exacto_dbfv_mul", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ, _P, _P, _P], C.c_int),
     ("exacto_dbfv_mul_dev", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ, _P, _P, _P], C.c_int),
     ("exacto_dbfv_mul_chain", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ, _SZ], C.c_int),
@@ -299,6 +307,21 @@ def dbfv_change_base_matrix(d: int, base: int, plain: int, new_base: int, new_d:
     return out[:new_d, :d]
 
 
+def dbfv_mul_plan(d: int, base: int, plain: int, symmetric: bool = False):
+    """The plan of dbfv_mul (or, symmetric, of dbfv_square) for the d output limbs, host only
+    (exacto_dbfv_mul_plan): (pairs [(i, j)], limbs [[(pair index, coefficient)]])."""
+    lib = load()
+    np_, nt = C.c_size_t(), C.c_size_t()
+    check(lib.exacto_dbfv_mul_plan(d, base, plain, int(symmetric), None, 0, C.byref(np_), None, None, 0, C.byref(nt)))
+    pairs = np.zeros((max(np_.value, 1), 2), dtype=np.int32)
+    start = np.zeros(d + 1, dtype=np.int32)
+    terms = np.zeros((max(nt.value, 1), 2), dtype=np.int64)
+    check(lib.exacto_dbfv_mul_plan(d, base, plain, int(symmetric), pairs.ctypes.data, np_.value, C.byref(np_),
+                                   start.ctypes.data, terms.ctypes.data, nt.value, C.byref(nt)))
+    limbs = [[(int(p), int(c)) for p, c in terms[start[k]:start[k + 1]]] for k in range(d)]
+    return [(int(i), int(j)) for i, j in pairs[:np_.value]], limbs
+
+
 def noise_budget_bits(noise: int, moduli, plain: int) -> int:
     """Bits left before the noise reaches floor(Delta / 2), Delta = floor(Q / p): max(0, bitlen(floor(Delta / 2))
     - bitlen(noise)), an exact integer."""
@@ -404,6 +427,10 @@ class HipContext:
     def set_chunk(self, chunk: int):
         check(self._lib.exacto_ctx_set_chunk(self._h, chunk))
 
+    def set_square_hook(self, on: bool):
+        """eval_poly's even baby steps on the square path (default) or as two-operand products (A/B)."""
+        check(self._lib.exacto_ctx_set_square_hook(self._h, 1 if on else 0))
+
     def synchronize(self):
         check(self._lib.exacto_synchronize(self._h))
 
@@ -456,6 +483,22 @@ class HipContext:
                                                  out.ctypes.data, B))
         return out
 
+    def bfv_square_no_relin(self, ct: np.ndarray) -> np.ndarray:
+        """ct [B][2][L][n] -> [B][3][L][n], bit for bit bfv_mul_no_relin(ct, ct)."""
+        ct = _u64(ct)
+        B = ct.shape[0]
+        out = np.zeros((B, 3, self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_bfv_square_no_relin(self._h, ct.ctypes.data, ct.shape[1], out.ctypes.data, B))
+        return out
+
+    def bfv_square_and_relin(self, ct: np.ndarray) -> np.ndarray:
+        """ct [B][2][L][n] -> [B][2][L][n], bit for bit bfv_mul_and_relin(ct, ct)."""
+        ct = _u64(ct)
+        B = ct.shape[0]
+        out = np.zeros((B, 2, self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_bfv_square_and_relin(self._h, ct.ctypes.data, out.ctypes.data, B))
+        return out
+
     def _addsub(self, fn, ct1, ct2):
         ct1, ct2 = _u64(ct1), _u64(ct2)
         B = ct1.shape[0]
@@ -487,6 +530,17 @@ class HipContext:
         dout = np.zeros(B, dtype=np.uint32)
         check(self._lib.exacto_dbfv_mul(self._h, d, base, plain, a.ctypes.data, b.ctypes.data,
                                         out.ctypes.data, B, _ptr(da), _ptr(db), dout.ctypes.data))
+        return out, dout
+
+    def dbfv_square(self, d, base, plain, a: np.ndarray, depth_a=None):
+        """a [B][d][2][L][n] -> (out, depth_out), bit for bit dbfv_mul(a, a, depth_a, depth_a)."""
+        a = _u64(a)
+        B = a.shape[0]
+        out = np.zeros_like(a)
+        da = np.ascontiguousarray(depth_a, dtype=np.uint32) if depth_a is not None else None
+        dout = np.zeros(B, dtype=np.uint32)
+        check(self._lib.exacto_dbfv_square(self._h, d, base, plain, a.ctypes.data, out.ctypes.data, B, _ptr(da),
+                                           dout.ctypes.data))
         return out, dout
 
     def dbfv_mul_chain(self, d, base, plain, x: np.ndarray, y: np.ndarray, depth: int):
@@ -776,6 +830,12 @@ class HipContext:
                                          out.ctypes.data, ct.shape[0]))
         return out
 
+    def eval_poly_dev(self, ct, coeffs, out, batch):
+        """The same on device buffers (coeffs on the host); asynchronous on the context's stream."""
+        cf = np.ascontiguousarray(np.asarray(coeffs, dtype=np.uint64))
+        check(self._lib.exacto_eval_poly_dev(self._h, self._p(ct), cf.ctypes.data if cf.size else None, cf.size,
+                                             self._p(out), batch))
+
     def _pt(self, pt, rows):
         pt = _u64(pt).reshape(rows, self.n)
         return pt
@@ -898,6 +958,12 @@ class HipContext:
         check(self._lib.exacto_bfv_mul_and_relin_dev(self._h, self._p(ct1), self._p(ct2),
                                                      self._p(out), batch))
 
+    def bfv_square_no_relin_dev(self, ct, out, batch, polys=2):
+        check(self._lib.exacto_bfv_square_no_relin_dev(self._h, self._p(ct), polys, self._p(out), batch))
+
+    def bfv_square_and_relin_dev(self, ct, out, batch):
+        check(self._lib.exacto_bfv_square_and_relin_dev(self._h, self._p(ct), self._p(out), batch))
+
     def bfv_apply_automorphism_dev(self, ct, element, gk, num_keys, out, batch):
         check(self._lib.exacto_bfv_apply_automorphism_dev(self._h, self._p(ct), 2, element, self._p(gk), num_keys,
                                                           self._p(out), batch))
@@ -911,6 +977,11 @@ class HipContext:
         db = np.ascontiguousarray(depth_b, dtype=np.uint32) if depth_b is not None else None
         check(self._lib.exacto_dbfv_mul_dev(self._h, d, base, plain, self._p(a), self._p(b),
                                             self._p(out), batch, _ptr(da), _ptr(db), None))
+
+    def dbfv_square_dev(self, d, base, plain, a, out, batch, depth_a=None):
+        da = np.ascontiguousarray(depth_a, dtype=np.uint32) if depth_a is not None else None
+        check(self._lib.exacto_dbfv_square_dev(self._h, d, base, plain, self._p(a), self._p(out), batch, _ptr(da),
+                                               None))
 
     def dbfv_encrypt_sk_dev(self, d, base, plain, values, sk, key, stream, ct, batch, sigma=3.2, poly=False):
         """values [B] (poly: pt [B][n]) on the device -> ct [B][d][2][L][n]."""

@@ -276,6 +276,7 @@ struct exacto_ctx {
     // products' tensors in the auxiliary primes (run_mul, dbfv_mul_core); psum_max = the largest
     // product count m with m (p n Q + 2) < P, so that the summed rounding stays liftable from P
     bool psum_env = true;
+    bool square_hook = true;     // eval_poly's baby steps x^(i/2) x^(i/2) on the square path (exacto_ctx_set_square_hook)
     int psum_max = 0;
     int psum_fp_max = 0;         // ... and with |sum| < P / 4, the rounded-float CRT over P (kernels.hip fpc_lift)
     bool fp_crt = true;          // EXACTO_FP_CRT=0: Garner over P in the SP scale kernels (A/B)
@@ -382,7 +383,7 @@ struct exacto_ctx {
     // product-sum plan cache (dbfv_mul's index rule, or bfv_mul_sum's term lists: cached_kind)
     u64* d_off = nullptr;
     size_t off_cap = 0;
-    int cached_kind = -1;            // 0: dbfv_plan, 1: mul_sum_plan; -1: none
+    int cached_kind = -1;            // 0: dbfv_plan, 1: mul_sum_plan, 2: dbfv_plan's symmetric form; -1: none
     std::vector<uint32_t> cached_ms; // mul_sum_plan: ia, ib, slot lists, then na, nb, nslots, group limit
     int cached_ngroups = 0;          // mul_sum_plan: groups of the cached plan (its "output limbs")
     int* d_slot_start = nullptr;     // ... and, when a slot has several, slot s = groups [start[s], start[s+1])
@@ -1234,6 +1235,12 @@ extern "C" int exacto_ctx_set_chunk(exacto_ctx* c, size_t chunk) {
     return 0;
 }
 
+extern "C" int exacto_ctx_set_square_hook(exacto_ctx* c, int on) {
+    if (!c) return invalid_param("null context");
+    c->square_hook = on != 0;
+    return 0;
+}
+
 extern "C" int exacto_synchronize(exacto_ctx* c) {
     if (!c) return invalid_param("null context");
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1354,7 +1361,8 @@ static bool scale_fold(const exacto_ctx* c) {
            exact_scale_fold_ok(c->L, c->K, crt_mode(c), c->fp_crt, c->fpq_lim);
 }
 
-static int run_inv_tensor(exacto_ctx* c, const Operands& o, int cnt, bool p2only = false, bool fold = false) {
+static int run_inv_tensor(exacto_ctx* c, const Operands& o, int cnt, bool p2only = false, bool fold = false,
+                          bool square = false) {
     const int NP = c->L + c->K;
     bool lazy = true;
     const bool near60 = tensor_asm(c);
@@ -1376,13 +1384,14 @@ static int run_inv_tensor(exacto_ctx* c, const Operands& o, int cnt, bool p2only
         bytes = pb * (c->L * (2.0 * cts + 3.0 * cnt) +
                       c->K * (p2only ? cts + (double)cnt : 2.0 * cts + 3.0 * cnt));
     } else {
-        bytes = cnt * (p2only ? pb * (7.0 * c->L + 3.0 * c->K) : pb * 7.0 * NP);
+        // (a square reads its one operand's two polynomials: 5 polys)
+        bytes = cnt * (p2only ? pb * (7.0 * c->L + 3.0 * c->K) : pb * (square ? 5.0 : 7.0) * NP);
     }
     ProfScope ps(c, PK_TENSOR, (u64)cnt * (p2only ? 3 * c->L + c->K : 3 * NP), bytes);
     // the exact path's scale kernels take T in [0, 2q) (shoup products, 30-bit-limb dot products with
     // headroom); the HPS scale subtracts residues as canonical
     launch_inv_tensor(o, c->ws_extP, c->ws_T, cnt, c->logn, c->L, c->K, lazy, c->d_primes, c->stream, near60, p2only,
-                      qbits, c->tensor_share_npairs, near60 && c->path != EXACTO_PATH_HPS, fold);
+                      qbits, c->tensor_share_npairs, near60 && c->path != EXACTO_PATH_HPS, fold, square);
     CHECK_LAUNCH();
     return 0;
 }
@@ -1614,8 +1623,11 @@ static int ensure_rs_wide(exacto_ctx* c) {
 // coef (optional): when the key switch runs over the integers (ks32), the last forward NTT is left
 // to the caller and *coef is set: out then holds the coefficient domain (a caller that first sums
 // products, as dbfv_mul does, transforms the sums instead of every product).
+// square: product p is op.a's ciphertext times itself (op.b is never read): steps 1-3 run over its two
+// polynomials only, coefQ[item] = [c0, c1] and extP[item] = [a0, a1] at a two-polynomial stride, and the
+// tensor takes its square form; from the scale on nothing differs.
 static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out_stride, bool relin,
-                   bool* coef = nullptr) {
+                   bool* coef = nullptr, bool square = false) {
     if (coef) *coef = false;
     if (c->deferred_code) return fail(c->deferred_code, c->deferred_msg);
     if (relin && !c->rlk_loaded) return fail(EXACTO_ERR_MISSING_KEY, "key not available: relinearization key not loaded");
@@ -1663,33 +1675,38 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
         LaneGuard lane(c, (int)((s / (long)C) % nl));
         Operands o = op;
         if (o.a_off) o.a_off += s; else o.a += s * o.a_stride;
-        if (o.b_off) o.b_off += s; else o.b += s * o.b_stride;
+        if (square) { o.b = nullptr; o.b_off = nullptr; }
+        else if (o.b_off) o.b_off += s; else o.b += s * o.b_stride;
         if (!o.ea) {
             // 1. inputs -> coefficient domain (INTT), coefQ[item] = [c0, c1, d0, d1][L][n]
+            // (square: [c0, c1][L][n])
+            const long ip = square ? 2 : 4;   // input polynomials per product
             NttBatch nb{};
             nb.src = o.a; nb.src_off = o.a_off; nb.src_item_stride = o.a_stride;
-            nb.dst = c->ws_coefQ; nb.dst_item_stride = 4 * Ln;
+            nb.dst = c->ws_coefQ; nb.dst_item_stride = ip * Ln;
             nb.ppi = 2 * L; nb.prime_base = 0; nb.period = L;
             if (int e = run_ntt(c, nb, (long)cnt * 2 * L, true)) return e;
-            nb.src = o.b; nb.src_off = o.b_off; nb.src_item_stride = o.b_stride;
-            nb.dst = c->ws_coefQ + 2 * Ln;
-            if (int e = run_ntt(c, nb, (long)cnt * 2 * L, true)) return e;
+            if (!square) {
+                nb.src = o.b; nb.src_off = o.b_off; nb.src_item_stride = o.b_stride;
+                nb.dst = c->ws_coefQ + 2 * Ln;
+                if (int e = run_ntt(c, nb, (long)cnt * 2 * L, true)) return e;
+            }
             // 2. extension to the auxiliary primes
             if (c->path == EXACTO_PATH_HPS) {
                 // per input poly: the q residues in, K auxiliary residues out
-                ProfScope pl(c, PK_HPS_EXT, 4ull * cnt, 8.0 * (1 + K) * n * 4.0 * cnt);
-                launch_hps_extend(c->ws_coefQ, c->ws_extP, 4L * cnt, n, c->d_primes, K, c->stream);
+                ProfScope pl(c, PK_HPS_EXT, (u64)ip * cnt, 8.0 * (1 + K) * n * (double)ip * cnt);
+                launch_hps_extend(c->ws_coefQ, c->ws_extP, ip * cnt, n, c->d_primes, K, c->stream);
             } else {
-                ProfScope pl(c, PK_LIFT, 4ull * cnt, 8.0 * (L + K) * n * 4.0 * cnt);
-                launch_exact_lift(c->ws_coefQ, c->ws_extP, 4L * cnt, n, c->d_crt, c->d_primes, L, K,
+                ProfScope pl(c, PK_LIFT, (u64)ip * cnt, 8.0 * (L + K) * n * (double)ip * cnt);
+                launch_exact_lift(c->ws_coefQ, c->ws_extP, ip * cnt, n, c->d_crt, c->d_primes, L, K,
                                   crt_mode(c), c->stream);
             }
             CHECK_LAUNCH();
             // 3. forward NTT of the extended polynomials (exact path with the asm tensor, its only
             // reader: outputs left in [0, 2q), which its products take)
-            NttBatch eb = contiguous(c->ws_extP, cnt, 4L * K, L, K, n);
+            NttBatch eb = contiguous(c->ws_extP, cnt, ip * K, L, K, n);
             eb.lazy_out = c->path != EXACTO_PATH_HPS && tensor_asm(c);
-            if (int e = run_ntt(c, eb, (long)cnt * 4 * K, false)) return e;
+            if (int e = run_ntt(c, eb, (long)cnt * ip * K, false)) return e;
         } else {
             o.ea_off += s;
             o.eb_off += s;
@@ -1697,7 +1714,7 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
         // 4+5. tensor product in every prime, fused into the inverse NTT of its components
         // (psum's readers of T, fpq_acc, sum up to 15 canonical z_i: they keep the unfolded form)
         const bool tfold = !ps.on && scale_fold(c);
-        if (int e = run_inv_tensor(c, o, cnt, ps.on, tfold)) return e;
+        if (int e = run_inv_tensor(c, o, cnt, ps.on, tfold, square)) return e;
         if (ps.on) {
             // the output limbs' c0 / c1 auxiliary residues, summed over their products, then inverse-
             // transformed: [ib][k][c][a][n] in extP (unused: the extensions are shared, steps 1-3 skipped)
@@ -1986,6 +2003,32 @@ extern "C" int exacto_bfv_mul_and_relin_dev(exacto_ctx* c, const uint64_t* ct1, 
     return run_mul(c, plain_operands(c, ct1, ct2), (long)B, out, 2L * c->L * c->n, true);
 }
 
+// ct (.) ct on the one-operand pipeline (run_mul square): bit for bit bfv_mul_*(ct, ct).  The checks and
+// their order are the two-operand call's; out must not overlap ct (the tensor reads ct after the first
+// chunks' results are written).
+static int bfv_square_dev(exacto_ctx* c, const u64* ct, u64* out, size_t B, bool relin) {
+    if (c->deferred_code) return fail(c->deferred_code, c->deferred_msg);
+    if (relin && !c->rlk_loaded) return fail(EXACTO_ERR_MISSING_KEY, "key not available: relinearization key not loaded");
+    if (B == 0) return 0;
+    if (!ct || !out) return invalid_param("null ciphertext pointer");
+    const size_t pw = (size_t)c->L * c->n;
+    if (ct < out + B * (relin ? 2 : 3) * pw && out < ct + B * 2 * pw)
+        return invalid_param("the output of a square must not overlap its input");
+    Operands op = plain_operands(c, ct, nullptr);
+    return run_mul(c, op, (long)B, out, (relin ? 2L : 3L) * c->L * c->n, relin, nullptr, true);
+}
+
+extern "C" int exacto_bfv_square_no_relin_dev(exacto_ctx* c, const uint64_t* ct, size_t polys, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (polys != 2) return invalid_param("multiplication requires degree-1 ciphertexts");
+    return bfv_square_dev(c, ct, out, B, false);
+}
+
+extern "C" int exacto_bfv_square_and_relin_dev(exacto_ctx* c, const uint64_t* ct, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    return bfv_square_dev(c, ct, out, B, true);
+}
+
 extern "C" int exacto_relinearize_dev(exacto_ctx* c, const uint64_t* ct, size_t polys, uint64_t* out, size_t B) {
     if (int e = check_ctx(c)) return e;
     const long Ln = (long)c->L * c->n;
@@ -2088,6 +2131,20 @@ extern "C" int exacto_bfv_mul_and_relin(exacto_ctx* c, const uint64_t* ct1, cons
                      [&](std::vector<u64*>& d, u64* o) { return exacto_bfv_mul_and_relin_dev(c, d[0], d[1], o, B); });
 }
 
+extern "C" int exacto_bfv_square_no_relin(exacto_ctx* c, const uint64_t* ct, size_t polys, uint64_t* out, size_t B) {
+    if (!c) return invalid_param("null context");
+    const size_t ctb = B * 2 * c->L * poly_bytes(c);
+    return host_call(c, {{ct, ctb}}, B * 3 * c->L * poly_bytes(c), out,
+                     [&](std::vector<u64*>& d, u64* o) { return exacto_bfv_square_no_relin_dev(c, d[0], polys, o, B); });
+}
+
+extern "C" int exacto_bfv_square_and_relin(exacto_ctx* c, const uint64_t* ct, uint64_t* out, size_t B) {
+    if (!c) return invalid_param("null context");
+    const size_t ctb = B * 2 * c->L * poly_bytes(c);
+    return host_call(c, {{ct, ctb}}, ctb, out,
+                     [&](std::vector<u64*>& d, u64* o) { return exacto_bfv_square_and_relin_dev(c, d[0], o, B); });
+}
+
 extern "C" int exacto_relinearize(exacto_ctx* c, const uint64_t* ct, size_t polys, uint64_t* out, size_t B) {
     if (!c) return invalid_param("null context");
     const size_t inb = B * polys * c->L * poly_bytes(c);
@@ -2187,36 +2244,61 @@ static int plan_upload(exacto_ctx* c, size_t B, size_t na, size_t nb, const std:
 // when the limbs of one dbfv_mul are split across GPUs): output slot s = limb limbs[s] gets the sum
 // over pairs (i, j) with i + j == limbs[s] plus the reps folding of the high limbs i + j >= d.  Only
 // the pairs some listed limb uses are multiplied.
-static int dbfv_plan(exacto_ctx* c, size_t B, size_t d, u64 base, u64 plain, const std::vector<int>& limbs) {
-    if (c->cached_kind == 0 && c->cached_B == B && c->cached_d == d && c->cached_base == base && c->cached_p == plain &&
-        c->d_off && c->cached_limbs == limbs)
-        return 0;
+// sym (dbfv_square: both operands are the same d ciphertexts, so products (i, j) and (j, i) are one
+// ciphertext): only the pairs i <= j are multiplied, and every limb's term list is the one above with
+// (j, i) replaced by the index of (i, j) -- a product shared by two ordered pairs is listed twice, term for
+// term in the same order and with the same coefficients, so the terms per limb (cached_sum_m, the
+// psum / ks32 bounds) and with them the key-switch mode are those of dbfv_mul(a, a).
+static void dbfv_plan_build(size_t d, u64 base, u64 plain, const std::vector<int>& limbs, bool sym,
+                            std::vector<std::pair<int, int>>& pairs, std::vector<int>& start,
+                            std::vector<CombineTerm>& terms) {
     const auto reps = small_reps(base, d, plain);
     const size_t dout = limbs.size();
     auto coef_of = [&](size_t i, size_t j, size_t ko) -> i64 {
         const size_t k = i + j;
         return k == ko ? 1 : k >= d ? reps[k - d][ko] : 0;
     };
-    std::vector<std::pair<int, int>> pairs;
+    // the ordered pairs some listed limb needs, and the product each reads
+    std::vector<std::pair<int, int>> ordered;
+    std::vector<int> index;
+    std::vector<int> of(d * d, -1);
+    pairs.clear();
     for (size_t i = 0; i < d; ++i)
         for (size_t j = 0; j < d; ++j) {
             bool needed = false;
             for (int ko : limbs) needed |= coef_of(i, j, (size_t)ko) != 0;
-            if (needed) pairs.push_back({(int)i, (int)j});
+            if (!needed) continue;
+            const size_t lo = sym ? std::min(i, j) : i, hi = sym ? std::max(i, j) : j;
+            if (of[lo * d + hi] < 0) {   // (sym: (lo, hi) comes first in this order, lo <= hi)
+                of[lo * d + hi] = (int)pairs.size();
+                pairs.push_back({(int)lo, (int)hi});
+            }
+            ordered.push_back({(int)i, (int)j});
+            index.push_back(of[lo * d + hi]);
         }
-    const int npairs = (int)pairs.size();
-    std::vector<int> start(dout + 1, 0);
-    std::vector<CombineTerm> terms;
+    start.assign(dout + 1, 0);
+    terms.clear();
     for (size_t so = 0; so < dout; ++so) {
         start[so] = (int)terms.size();
-        for (int pi = 0; pi < npairs; ++pi) {
-            const i64 coef = coef_of(pairs[pi].first, pairs[pi].second, (size_t)limbs[so]);
-            if (coef != 0) terms.push_back({pi, 0, coef});
+        for (size_t oi = 0; oi < ordered.size(); ++oi) {
+            const i64 coef = coef_of(ordered[oi].first, ordered[oi].second, (size_t)limbs[so]);
+            if (coef != 0) terms.push_back({index[oi], 0, coef});
         }
     }
     start[dout] = (int)terms.size();
+}
+
+static int dbfv_plan(exacto_ctx* c, size_t B, size_t d, u64 base, u64 plain, const std::vector<int>& limbs,
+                     bool sym = false) {
+    if (c->cached_kind == (sym ? 2 : 0) && c->cached_B == B && c->cached_d == d && c->cached_base == base && c->cached_p == plain &&
+        c->d_off && c->cached_limbs == limbs)
+        return 0;
+    std::vector<std::pair<int, int>> pairs;
+    std::vector<int> start;
+    std::vector<CombineTerm> terms;
+    dbfv_plan_build(d, base, plain, limbs, sym, pairs, start, terms);
     if (int e = plan_upload(c, B, d, d, pairs, start, terms)) return e;
-    c->cached_kind = 0;
+    c->cached_kind = sym ? 2 : 0;
     c->cached_d = d; c->cached_base = base; c->cached_p = plain;
     c->cached_limbs = limbs;
     return 0;
@@ -2282,6 +2364,29 @@ static int dbfv_params_check(size_t d, uint64_t base, uint64_t plain) {
     return 0;
 }
 
+// The plan dbfv_mul (symmetric = 0) or dbfv_square (1) runs for all d output limbs, pure host code.
+extern "C" int exacto_dbfv_mul_plan(size_t d, uint64_t base, uint64_t plain, int symmetric, int32_t* pairs,
+                                    size_t pair_cap, size_t* npairs, int32_t* term_start, int64_t* terms,
+                                    size_t term_cap, size_t* nterms) {
+    if (int e = dbfv_params_check(d, base, plain)) return e;
+    if (!npairs || !nterms) return invalid_param("null count pointer");
+    std::vector<int> limbs;
+    for (size_t k = 0; k < d; ++k) limbs.push_back((int)k);
+    std::vector<std::pair<int, int>> pr;
+    std::vector<int> start;
+    std::vector<CombineTerm> tm;
+    dbfv_plan_build(d, base, plain, limbs, symmetric != 0, pr, start, tm);
+    *npairs = pr.size();
+    *nterms = tm.size();
+    if (pairs && pair_cap >= pr.size())
+        for (size_t i = 0; i < pr.size(); ++i) { pairs[2 * i] = pr[i].first; pairs[2 * i + 1] = pr[i].second; }
+    if (term_start)
+        for (size_t k = 0; k <= d; ++k) term_start[k] = start[k];
+    if (terms && term_cap >= tm.size())
+        for (size_t i = 0; i < tm.size(); ++i) { terms[2 * i] = tm[i].pair; terms[2 * i + 1] = tm[i].coef; }
+    return 0;
+}
+
 // Every input ciphertext of a dBFV product batch enters d products (dbfv/eval.rs:109-122): its
 // inverse NTT, its exact (or HPS) extension to the auxiliary primes and their forward NTT
 // (pipeline steps 1-3) are computed here once per ciphertext, ext = [ct][2][K][n], instead of
@@ -2325,8 +2430,9 @@ static int extend_cts(exacto_ctx* c, const u64* cts, size_t ncts, u64* ext, cons
 // (bfv_mul_sum with more products per slot than one key switch lifts): the dout outputs are groups,
 // formed in gsum_buf and added per slot (mul_sum_plan's slot_start) before the forward transform of
 // out = [B][nslots][2][L][n].  *mode: the key switch taken, exacto_ctx_info.dbfv_key_switch's codes.
+// same_ab (the symmetric plan, b == a and nb == na): the extensions are made once, ext_b is ext_a.
 static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a, const uint64_t* b, uint64_t* out,
-                         size_t B, bool b_extended, size_t dout, size_t nslots, int* mode) {
+                         size_t B, bool b_extended, size_t dout, size_t nslots, int* mode, bool same_ab = false) {
     const int npairs = c->cached_npairs;
     const bool grouped = nslots < dout;
     const long Ln2 = 2L * c->L * c->n;
@@ -2347,12 +2453,12 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
             if (int e = extend_cts(c, a, B * na, c->ext_a, c->coef_in)) return e;
         }
         c->ext_a_ready = false;
-        if (!b_extended) {
+        if (!b_extended && !same_ab) {
             if (grow(&c->ext_b, &c->ext_b_cap, bytes_b)) return EXACTO_ERR_HIP;
             if (int e = extend_cts(c, b, B * nb, c->ext_b)) return e;
         }
         op.ea = c->ext_a; op.ea_off = c->d_off + 2 * BP;
-        op.eb = c->ext_b; op.eb_off = c->d_off + 3 * BP;
+        op.eb = same_ab ? c->ext_a : c->ext_b; op.eb_off = c->d_off + 3 * BP;
     }
     // the per-limb sums (dbfv/eval.rs:124-132) and the degree reduction are linear, so with ks32 they
     // run on the products' coefficient-domain results and only the d output limbs are transformed
@@ -2454,7 +2560,8 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
     }
     bool coef = false;
     if (op.ea) {
-        c->tensor_share_d = (int)((na + nb + 1) / 2);
+        // (distinct ciphertexts per item / 2; a square's d count as 2 ceil(d / 2) in the byte estimate)
+        c->tensor_share_d = (int)(((same_ab ? na : na + nb) + 1) / 2);
         c->tensor_share_npairs = npairs;
     }
     const int rc = run_mul(c, op, P, c->prod, Ln2, true, &coef);
@@ -2555,9 +2662,9 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
 // out = [B][dout][2][L][n] for the output limbs `limbs` (dout = limbs.size()), one group of items
 static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* a,
                           const uint64_t* b, uint64_t* out, size_t B, bool b_extended,
-                          const std::vector<int>* limbs) {
-    if (int e = dbfv_plan(c, B, d, base, plain, *limbs)) return e;
-    return mul_group_run(c, d, d, a, b, out, B, b_extended, limbs->size(), limbs->size(), &c->last_dbfv_ks);
+                          const std::vector<int>* limbs, bool square = false) {
+    if (int e = dbfv_plan(c, B, d, base, plain, *limbs, square)) return e;
+    return mul_group_run(c, d, d, a, b, out, B, b_extended, limbs->size(), limbs->size(), &c->last_dbfv_ks, square);
 }
 
 // Every buffer of a dbfv_mul pass grows with its item count (the products' results and digits, their
@@ -2569,7 +2676,7 @@ static int dbfv_mul_group(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
 // the output limbs `limbs` (nullptr: all d).
 static int dbfv_mul_core(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* a,
                          const uint64_t* b, uint64_t* out, size_t B, bool b_extended,
-                         const std::vector<int>* limbs = nullptr) {
+                         const std::vector<int>* limbs = nullptr, bool square = false) {
     std::vector<int> all;
     if (!limbs) {
         for (size_t k = 0; k < d; ++k) all.push_back((int)k);
@@ -2582,7 +2689,7 @@ static int dbfv_mul_core(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
                             n * G * (d * d * 2 + d * (4 + 4 * S)) +         // digits, sums, residues
                             4 * n * d * 2 * L * S;                          // key-switch sums
     const size_t Bg = std::max<size_t>(1, budget / std::max<size_t>(per_item, 1));
-    if (B <= Bg) return dbfv_mul_group(c, d, base, plain, a, b, out, B, b_extended, limbs);
+    if (B <= Bg) return dbfv_mul_group(c, d, base, plain, a, b, out, B, b_extended, limbs, square);
     // several groups: no coefficient-form carry between chain steps (its buffers are whole-batch)
     c->coef_in = nullptr;
     c->coef_slot = -1;
@@ -2591,7 +2698,7 @@ static int dbfv_mul_core(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
         const size_t cnt = std::min(Bg, B - g0);
         // b's extensions are per group here (a chain recomputes them for each group)
         if (int e = dbfv_mul_group(c, d, base, plain, a + g0 * d * ctw, b + g0 * d * ctw, out + g0 * dout * ctw, cnt,
-                                   false, limbs))
+                                   false, limbs, square))
             return e;
     }
     return 0;
@@ -2641,6 +2748,29 @@ extern "C" int exacto_dbfv_mul_dev(exacto_ctx* c, size_t d, uint64_t base, uint6
     const size_t w = d * 2 * c->L * (size_t)c->n;
     if (int e = split_run(c, B, 2, [&](exacto_ctx* x, size_t i0, size_t cnt) {
             return dbfv_mul_core(x, d, base, plain, a + i0 * w, b + i0 * w, out + i0 * w, cnt, false);
+        }))
+        return e;
+    if (depth_out)
+        for (size_t i = 0; i < B; ++i) depth_out[i] = 1;
+    return 0;
+}
+
+// dbfv_mul(a, a) with the symmetric plan (dbfv_plan sym): d (d + 1) / 2 of the d^2 products, the operand's
+// extensions made once.  The checks and the depth guard are exacto_dbfv_mul_dev's with depth_b = depth_a.
+extern "C" int exacto_dbfv_square_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* a,
+                                      uint64_t* out, size_t B, const uint32_t* depth_a, uint32_t* depth_out) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = dbfv_params_check(d, base, plain)) return e;
+    for (size_t i = 0; i < B; ++i)
+        if ((depth_a ? depth_a[i] : 0) + 1 > 1)
+            return fail(EXACTO_ERR_NOT_IMPLEMENTED, "not yet implemented: chained dBFV multiplication requires "
+                                                    "ciphertext-level lattice reduction (paper §4.6.2)");
+    if (B == 0) return 0;
+    const size_t w = d * 2 * c->L * (size_t)c->n;
+    if (!a || !out) return invalid_param("null ciphertext pointer");
+    if (a < out + B * w && out < a + B * w) return invalid_param("the output of a square must not overlap its input");
+    if (int e = split_run(c, B, 2, [&](exacto_ctx* x, size_t i0, size_t cnt) {
+            return dbfv_mul_core(x, d, base, plain, a + i0 * w, a + i0 * w, out + i0 * w, cnt, false, nullptr, true);
         }))
         return e;
     if (depth_out)
@@ -3153,6 +3283,15 @@ extern "C" int exacto_dbfv_mul_chain(exacto_ctx* c, size_t d, uint64_t base, uin
     const size_t bytes = B * d * 2 * c->L * poly_bytes(c);
     return host_call(c, {{x, bytes}, {y, bytes}}, bytes, out, [&](std::vector<u64*>& dv, u64* o) {
         return exacto_dbfv_mul_chain_dev(c, d, base, plain, dv[0], dv[1], o, B, depth);
+    });
+}
+
+extern "C" int exacto_dbfv_square(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* a,
+                                  uint64_t* out, size_t B, const uint32_t* depth_a, uint32_t* depth_out) {
+    if (!c) return invalid_param("null context");
+    const size_t bytes = B * d * 2 * c->L * poly_bytes(c);
+    return host_call(c, {{a, bytes}}, bytes, out, [&](std::vector<u64*>& dv, u64* o) {
+        return exacto_dbfv_square_dev(c, d, base, plain, dv[0], o, B, depth_a, depth_out);
     });
 }
 
@@ -3892,7 +4031,7 @@ extern "C" int exacto_trivial_encrypt_dev(exacto_ctx* c, const uint64_t* pt, uin
 
 // eval_poly_homomorphic (digit_extract.rs:101-157), batched: the same polynomial on B ciphertexts.
 // Paterson-Stockmeyer with the reference's schedule: baby steps x^i = x^(i/2) * x^(i - i/2) for
-// i = 2..k, k = max(2, ceil(sqrt(d + 1))); groups g_i = sum_j a_{ik+j} x^j (trivial(0) + scalar
+// i = 2..k (even i on the one-operand square pipeline), k = max(2, ceil(sqrt(d + 1))); groups g_i = sum_j a_{ik+j} x^j (trivial(0) + scalar
 // multiples, coefficients reduced mod t as bfv_scalar_mul does); Horner in x^k.  Uses the context's
 // resident relinearisation key for every bfv_mul_and_relin.
 extern "C" int exacto_eval_poly_dev(exacto_ctx* c, const uint64_t* ct, const uint64_t* coeffs, size_t m,
@@ -3930,7 +4069,10 @@ extern "C" int exacto_eval_poly_dev(exacto_ctx* c, const uint64_t* ct, const uin
     if (hipGetLastError() != hipSuccess) rc = fail(EXACTO_ERR_HIP, "HIP error: trivial launch");
     for (size_t i = 2; i <= k && rc == 0; ++i) {
         const size_t half = i / 2;
-        rc = exacto_bfv_mul_and_relin_dev(c, baby[half], baby[i - half], slot(i), B);
+        // (even i: a square, bit for bit the product of baby[half] with itself)
+        rc = (i - half == half && c->square_hook)
+                 ? exacto_bfv_square_and_relin_dev(c, baby[half], slot(i), B)
+                 : exacto_bfv_mul_and_relin_dev(c, baby[half], baby[i - half], slot(i), B);
         baby[i] = slot(i);
     }
     // group g_i into `dst`: trivial(0) + sum_j (a mod t) x^j

@@ -193,7 +193,10 @@ void launch_drop_prime(const u64* in, u64* out, long rows, int l, bool round, co
 // psum; asm_inv and n = 4096 / 8192 only)
 void launch_inv_tensor(const Operands& op, const u64* extP, u64* T, int items, int logn, int L, int K, bool lazy,
                        const PrimeConst* primes, hipStream_t s, bool asm_inv = false, bool p2only = false,
-                       int qbits = 64, int share_np = 0, bool lazy_out = false, bool fold = false);
+                       int qbits = 64, int share_np = 0, bool lazy_out = false, bool fold = false,
+                       bool square = false);
+// square: op.a times itself (ntt_inv_tensor_kernel SQ): op.b / op.eb are never read and extP holds two
+// polynomials per item, [item][a0,a1][K][n]; never with p2only
 // fold: T holds the folded scale's form (ntt_inv_tensor_kernel FOLD); the caller asked crt_fold_tensor_ok and
 // hands the same decision to launch_exact_scale
 bool crt_fold_tensor_ok(int logn, bool asm_inv, bool lazy_out);

@@ -936,10 +936,19 @@ __device__ __forceinline__ void tensor_block(long b, long total, int per, int L,
 // LZO (ASM only): outputs in [0, 2q), as ntt_inv_tensor_pin_kernel
 // FOLD (ASM only): the last stage's constants carry the prime's scale factor (PrimeConst::fold_*), so
 // T holds z_i = T_i p (Q / q_i)^-1 mod q_i and T_a fpc_pq[a] mod p_a, in the range T_i and T_a had
+// SQ: the square of one ciphertext (op.a; op.b / op.eb are never read, extP is [item][a0,a1][K][n]):
+//   c0 = a0*a0,  c1 = 2 a0*a1,  c2 = a1*a1
+// c0 / c2 load one polynomial, c1 forms one product and doubles it.  Every product flavour is a function
+// of the 128-bit a b alone, so a0*a1 is the very value both of the two-operand c1's products have and the
+// doubled one is their sum: the same bound (< 4q, or the non-lazy forms' < q) and the same bits out.
 template <int LOGN, bool LAZY, bool ASM = false, int PROBE = 0, bool GEN = false, int QB = 60, bool LZO = false,
-          bool FOLD = false>
+          bool FOLD = false, bool SQ = false>
 __global__ void __launch_bounds__((1 << LOGN) / 16 < 64 ? 64 : (1 << LOGN) / 16)
-__attribute__((amdgpu_waves_per_eu(3)))  // the ASM form otherwise takes 184 VGPRs (2 waves/SIMD)
+// the ASM form otherwise takes 184 VGPRs (2 waves/SIMD).  The C++ square forms hold no more values than their
+// two-operand twins, but with 168 VGPRs allowed the scheduler spends a few more than 128 on some of them
+// where the twins sit at 4 waves/SIMD: those are held at 4.  Not n = 256 (both twins at 3) and not the
+// non-lazy form at n = 2048 (130 VGPRs, 3 waves; held at 4 it spills 3 dwords)
+__attribute__((amdgpu_waves_per_eu(SQ && !ASM && !GEN && LOGN != 8 && !(LOGN == 11 && !LAZY) ? 4 : 3)))
 ntt_inv_tensor_kernel(Operands op, const u64* __restrict__ extP, u64* __restrict__ Tout, int L, int K,
                       const PrimeConst* __restrict__ primes, int remap, int p2only = 0, int share_np = 0) {
     constexpr int N = 1 << LOGN;
@@ -964,7 +973,19 @@ ntt_inv_tensor_kernel(Operands op, const u64* __restrict__ extP, u64* __restrict
     const PrimeConst& P = primes[t];
     // the four operand polynomials of (item, prime t)
     auto operands = [&](long it, int tt, const u64*& A0, const u64*& A1, const u64*& B0, const u64*& B1) {
-        if (tt < L) {
+        if constexpr (SQ) {
+            B0 = B1 = nullptr;
+            if (tt < L) {
+                const u64* A = op.a + (op.a_off ? (long)op.a_off[it] : it * op.a_stride);
+                A0 = A + (long)tt * N; A1 = A + (long)(L + tt) * N;
+            } else if (op.ea) {
+                const u64* EA = op.ea + (long)op.ea_off[it] + (long)(tt - L) * N;
+                A0 = EA; A1 = EA + (long)K * N;
+            } else {
+                const u64* E = extP + it * 2 * K * N + (long)(tt - L) * N;
+                A0 = E; A1 = E + (long)K * N;
+            }
+        } else if (tt < L) {
             const u64* A = op.a + (op.a_off ? (long)op.a_off[it] : it * op.a_stride);
             const u64* B = op.b + (op.b_off ? (long)op.b_off[it] : it * op.b_stride);
             A0 = A + (long)tt * N; A1 = A + (long)(L + tt) * N;
@@ -998,7 +1019,55 @@ ntt_inv_tensor_kernel(Operands op, const u64* __restrict__ extP, u64* __restrict
         }
     };
     u64 x[16], y[16];
-    if (c != 1) {
+    if constexpr (SQ && LOGN <= 7) {
+        // n <= 128 (one wave, mostly idle lanes): one product path for the three components, x = A0 (c0, c1)
+        // or A1 (c2), y = A1 (c1) or x itself.  (The two-branch form below took up to 134 VGPRs here, 3
+        // waves/SIMD where the two-operand kernels sit at 4; this one spilled at n >= 1024.)
+        load(c == 2 ? A1 : A0, x);
+        if (c == 1) {
+            load(A1, y);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) y[k] = x[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) x[k] = mulr(x[k], y[k]);
+        if (c == 1) {
+            const u64 q = P.q, q2 = P.two_q;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const u64 v = x[k] + x[k];
+                x[k] = LAZY ? (v >= q2 ? v - q2 : v) : (v >= q ? v - q : v);
+            }
+        }
+    } else if constexpr (SQ) {
+        const u64 q = P.q, q2 = P.two_q;
+        if (c != 1) {
+            load(c == 0 ? A0 : A1, x);
+            if constexpr (ASM) {
+                mul16_near60(x, x, x, dq);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) x[k] = mulr(x[k], x[k]);
+            }
+        } else {
+            // 2 a0 a1: the two-operand sum of two equal products, under the same bound
+            load(A0, x);
+            load(A1, y);
+            if constexpr (ASM) {
+                mul16_near60(x, x, y, dq);
+#pragma unroll
+                for (int k = 0; k < 16; ++k) x[k] += x[k];   // < 4q
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const u64 z = mulr(x[k], y[k]);
+                    const u64 v = z + z;
+                    x[k] = GEN ? v : LAZY ? (v >= q2 ? v - q2 : v) : (v >= q ? v - q : v);
+                }
+            }
+        }
+    } else if (c != 1) {
         load(c == 0 ? A0 : A1, x);
         load(c == 0 ? B0 : B1, y);
         if constexpr (ASM) {
@@ -1055,7 +1124,8 @@ ntt_inv_tensor_kernel(Operands op, const u64* __restrict__ extP, u64* __restrict
 // workgroups per CU).  Same blocks, remap and p2only as ntt_inv_tensor_kernel.
 // LZO: outputs in [0, 2q) (the exact path's scale kernels take them; never for HPS, whose scale
 // subtracts residues as canonical); FOLD: as ntt_inv_tensor_kernel
-template <int LOGN, bool LZO = false, bool FOLD = false>
+// SQ: as ntt_inv_tensor_kernel's (each evaluation of A0 / A1 loaded once; c1 one product, doubled)
+template <int LOGN, bool LZO = false, bool FOLD = false, bool SQ = false>
 __global__ void __launch_bounds__((1 << LOGN) / 16) __attribute__((amdgpu_waves_per_eu(4)))
 ntt_inv_tensor_pin_kernel(Operands op, const u64* __restrict__ extP, u64* __restrict__ Tout, int L, int K,
                           const PrimeConst* __restrict__ primes, int remap, int p2only, int share_np) {
@@ -1072,8 +1142,19 @@ ntt_inv_tensor_pin_kernel(Operands op, const u64* __restrict__ extP, u64* __rest
     int t, c;
     tensor_unit(rem, L, p2only, t, c);
     const PrimeConst& P = primes[t];
-    const u64 *A0, *A1, *B0, *B1;
-    if (t < L) {
+    const u64 *A0, *A1, *B0 = nullptr, *B1 = nullptr;
+    if constexpr (SQ) {
+        if (t < L) {
+            const u64* A = op.a + (op.a_off ? (long)op.a_off[item] : item * op.a_stride);
+            A0 = A + (long)t * N; A1 = A + (long)(L + t) * N;
+        } else if (op.ea) {
+            const u64* EA = op.ea + (long)op.ea_off[item] + (long)(t - L) * N;
+            A0 = EA; A1 = EA + (long)K * N;
+        } else {
+            const u64* E = extP + item * 2 * K * N + (long)(t - L) * N;
+            A0 = E; A1 = E + (long)K * N;
+        }
+    } else if (t < L) {
         const u64* A = op.a + (op.a_off ? (long)op.a_off[item] : item * op.a_stride);
         const u64* B = op.b + (op.b_off ? (long)op.b_off[item] : item * op.b_stride);
         A0 = A + (long)t * N; A1 = A + (long)(L + t) * N;
@@ -1092,7 +1173,32 @@ ntt_inv_tensor_pin_kernel(Operands op, const u64* __restrict__ extP, u64* __rest
     constexpr int T = N / 16;
     const int vo = tid * 8;
 #define LDE(r_, k_) r_.ld64(vo, (k_) * T * 8)
-    if (c != 1) {
+    if constexpr (SQ) {
+        if (c != 1) {
+            const PolyRd sa(c == 0 ? A0 : A1, N * 8);
+#define PIN_S1(k0, k1)                                             \
+            {                                                      \
+                u64 r0_, r1_;                                      \
+                const u64 a0_ = LDE(sa, k0), a1_ = LDE(sa, k1);    \
+                MulNear60PinAsm<2>::run(r0_, r1_, a0_, a0_, a1_, a1_, dq, e16); \
+                PIN_SET(k0, r0_) PIN_SET(k1, r1_)                  \
+            }
+            PIN_S1(0, 1) PIN_S1(2, 3) PIN_S1(4, 5) PIN_S1(6, 7)
+            PIN_S1(8, 9) PIN_S1(10, 11) PIN_S1(12, 13) PIN_S1(14, 15)
+#undef PIN_S1
+        } else {
+            const PolyRd sa0(A0, N * 8), sa1(A1, N * 8);
+#define PIN_S2(k0, k1)                                             \
+            {                                                      \
+                u64 r0_, r1_;                                      \
+                MulNear60PinAsm<2>::run(r0_, r1_, LDE(sa0, k0), LDE(sa1, k0), LDE(sa0, k1), LDE(sa1, k1), dq, e16); \
+                PIN_SET(k0, r0_ + r0_) PIN_SET(k1, r1_ + r1_)      \
+            }
+            PIN_S2(0, 1) PIN_S2(2, 3) PIN_S2(4, 5) PIN_S2(6, 7)
+            PIN_S2(8, 9) PIN_S2(10, 11) PIN_S2(12, 13) PIN_S2(14, 15)
+#undef PIN_S2
+        }
+    } else if (c != 1) {
         const PolyRd sa(c == 0 ? A0 : A1, N * 8), sb(c == 0 ? B0 : B1, N * 8);
 #define PIN_T1(k0, k1)                                                   \
         {                                                          \
@@ -1547,7 +1653,8 @@ static bool gen_small(int qbits) {
     return on && gen_qb<LOGN>() < 60 && qbits <= gen_qb<LOGN>();
 }
 
-template <int LOGN>
+// SQ: the square instantiations (one operand; never with p2only)
+template <int LOGN, bool SQ = false>
 static void launch_it(const Operands& op, const u64* extP, u64* T, long blocks, int L, int K, bool lazy,
                       const PrimeConst* primes, hipStream_t s, bool asm_inv = false, int p2only = 0, int qbits = 64,
                       int np = 0, bool lzo = false, bool fold = false) {
@@ -1560,17 +1667,17 @@ static void launch_it(const Operands& op, const u64* extP, u64* T, long blocks, 
 #if EXACTO_CRT_FOLD
             if constexpr (LOGN == 12) {
                 if (lzo && fold) {
-                    EXACTO_LAUNCH((ntt_inv_tensor_pin_kernel<LOGN, true, true>), dim3(b2), dim3(threads), 0, s, op,
+                    EXACTO_LAUNCH((ntt_inv_tensor_pin_kernel<LOGN, true, true, SQ>), dim3(b2), dim3(threads), 0, s, op,
                                        extP, T, L, K, primes, remap, p2only, np);
                     return;
                 }
             }
 #endif
             if (lzo)
-                EXACTO_LAUNCH((ntt_inv_tensor_pin_kernel<LOGN, true>), dim3(b2), dim3(threads), 0, s, op, extP, T,
+                EXACTO_LAUNCH((ntt_inv_tensor_pin_kernel<LOGN, true, false, SQ>), dim3(b2), dim3(threads), 0, s, op, extP, T,
                                    L, K, primes, remap, p2only, np);
             else
-                EXACTO_LAUNCH((ntt_inv_tensor_pin_kernel<LOGN>), dim3(b2), dim3(threads), 0, s, op, extP, T, L,
+                EXACTO_LAUNCH((ntt_inv_tensor_pin_kernel<LOGN, false, false, SQ>), dim3(b2), dim3(threads), 0, s, op, extP, T, L,
                                    K, primes, remap, p2only, np);
             return;
         }
@@ -1579,17 +1686,17 @@ static void launch_it(const Operands& op, const u64* extP, u64* T, long blocks, 
 #if EXACTO_CRT_FOLD
             if constexpr (LOGN == 12) {
                 if (lzo && fold) {
-                    EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, true, 0, false, 60, true, true>), dim3(b2),
+                    EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, true, 0, false, 60, true, true, SQ>), dim3(b2),
                                        dim3(threads), 0, s, op, extP, T, L, K, primes, remap, p2only, np);
                     return;
                 }
             }
 #endif
             if (lzo)
-                EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, true, 0, false, 60, true>), dim3(b2),
+                EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, true, 0, false, 60, true, false, SQ>), dim3(b2),
                                    dim3(threads), 0, s, op, extP, T, L, K, primes, remap, p2only, np);
             else
-                EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, true>), dim3(b2), dim3(threads), 0, s, op, extP,
+                EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, true, 0, false, 60, false, false, SQ>), dim3(b2), dim3(threads), 0, s, op, extP,
                                    T, L, K, primes, remap, p2only, np);
             return;
         }
@@ -1597,19 +1704,19 @@ static void launch_it(const Operands& op, const u64* extP, u64* T, long blocks, 
     if constexpr (LOGN == 10 || LOGN == 12 || LOGN == 13) {
         if (lazy && !p2only && ntt_gen_on()) {   // every prime below 2^60: the generated generic-prime rounds
             if (gen_small<LOGN>(qbits))
-                EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, false, 0, true, gen_qb<LOGN>()>), dim3(blocks),
+                EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, false, 0, true, gen_qb<LOGN>(), false, false, SQ>), dim3(blocks),
                                    dim3(threads), 0, s, op, extP, T, L, K, primes, remap, 0, np);
             else
-                EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, false, 0, true>), dim3(blocks), dim3(threads), 0,
+                EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, false, 0, true, 60, false, false, SQ>), dim3(blocks), dim3(threads), 0,
                                    s, op, extP, T, L, K, primes, remap, 0, np);
             return;
         }
     }
     if (lazy)
-        EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true>), dim3(blocks), dim3(threads), 0, s, op, extP, T, L, K,
+        EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, true, false, 0, false, 60, false, false, SQ>), dim3(blocks), dim3(threads), 0, s, op, extP, T, L, K,
                            primes, remap);
     else
-        EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, false>), dim3(blocks), dim3(threads), 0, s, op, extP, T, L,
+        EXACTO_LAUNCH((ntt_inv_tensor_kernel<LOGN, false, false, 0, false, 60, false, false, SQ>), dim3(blocks), dim3(threads), 0, s, op, extP, T, L,
                            K, primes, remap);
 }
 
@@ -1619,9 +1726,10 @@ bool crt_fold_tensor_ok(int logn, bool asm_inv, bool lazy_out) {
     return EXACTO_CRT_FOLD && EXACTO_MUL_ASM && logn == 12 && asm_inv && lazy_out;
 }
 
-void launch_inv_tensor(const Operands& op, const u64* extP, u64* T, int items, int logn, int L, int K, bool lazy,
-                       const PrimeConst* primes, hipStream_t s, bool asm_inv, bool p2only, int qbits, int share_np,
-                       bool lazy_out, bool fold) {
+template <bool SQ>
+static void launch_inv_tensor_t(const Operands& op, const u64* extP, u64* T, int items, int logn, int L, int K, bool lazy,
+                                const PrimeConst* primes, hipStream_t s, bool asm_inv, bool p2only, int qbits,
+                                int share_np, bool lazy_out, bool fold) {
     // prime-major block order needs whole dBFV items in the launch (tensor_block)
     // (measured: cfg5, 36 products per item, tensor 270 -> 261 us; cfg4's 3 products per item and
     // u64_dbfv within noise: applied from 8 products per item; round 6 again at cfg4:
@@ -1630,27 +1738,40 @@ void launch_inv_tensor(const Operands& op, const u64* extP, u64* T, int items, i
     const long blocks = (long)items * 3 * (L + K);
     if (blocks == 0) return;
     if (p2only) {   // the caller checks asm_inv and n = 4096 / 8192
-        if (logn == 12) launch_it<12>(op, extP, T, blocks, L, K, lazy, primes, s, true, 1, 64, share_np, lazy_out);
-        else if (logn == 13) launch_it<13>(op, extP, T, blocks, L, K, lazy, primes, s, true, 1, 64, share_np, lazy_out);
+        if constexpr (!SQ) {
+            if (logn == 12) launch_it<12>(op, extP, T, blocks, L, K, lazy, primes, s, true, 1, 64, share_np, lazy_out);
+            else if (logn == 13) launch_it<13>(op, extP, T, blocks, L, K, lazy, primes, s, true, 1, 64, share_np, lazy_out);
+        }
         return;
     }
     switch (logn) {
-        case 4: launch_it<4>(op, extP, T, blocks, L, K, lazy, primes, s); break;
-        case 5: launch_it<5>(op, extP, T, blocks, L, K, lazy, primes, s); break;
-        case 6: launch_it<6>(op, extP, T, blocks, L, K, lazy, primes, s); break;
-        case 7: launch_it<7>(op, extP, T, blocks, L, K, lazy, primes, s); break;
-        case 8: launch_it<8>(op, extP, T, blocks, L, K, lazy, primes, s); break;
-        case 9: launch_it<9>(op, extP, T, blocks, L, K, lazy, primes, s); break;
-        case 10: launch_it<10>(op, extP, T, blocks, L, K, lazy, primes, s, false, 0, qbits, share_np); break;
-        case 11: launch_it<11>(op, extP, T, blocks, L, K, lazy, primes, s); break;
+        case 4: launch_it<4, SQ>(op, extP, T, blocks, L, K, lazy, primes, s); break;
+        case 5: launch_it<5, SQ>(op, extP, T, blocks, L, K, lazy, primes, s); break;
+        case 6: launch_it<6, SQ>(op, extP, T, blocks, L, K, lazy, primes, s); break;
+        case 7: launch_it<7, SQ>(op, extP, T, blocks, L, K, lazy, primes, s); break;
+        case 8: launch_it<8, SQ>(op, extP, T, blocks, L, K, lazy, primes, s); break;
+        case 9: launch_it<9, SQ>(op, extP, T, blocks, L, K, lazy, primes, s); break;
+        case 10: launch_it<10, SQ>(op, extP, T, blocks, L, K, lazy, primes, s, false, 0, qbits, share_np); break;
+        case 11: launch_it<11, SQ>(op, extP, T, blocks, L, K, lazy, primes, s); break;
         case 12:
-            launch_it<12>(op, extP, T, blocks, L, K, lazy, primes, s, asm_inv, 0, qbits, share_np, lazy_out,
-                          fold && crt_fold_tensor_ok(logn, asm_inv, lazy_out));
+            launch_it<12, SQ>(op, extP, T, blocks, L, K, lazy, primes, s, asm_inv, 0, qbits, share_np, lazy_out,
+                              fold && crt_fold_tensor_ok(logn, asm_inv, lazy_out));
             break;
-        case 13: launch_it<13>(op, extP, T, blocks, L, K, lazy, primes, s, asm_inv, 0, qbits, share_np, lazy_out); break;
-        case 14: launch_it<14>(op, extP, T, blocks, L, K, lazy, primes, s); break;
+        case 13: launch_it<13, SQ>(op, extP, T, blocks, L, K, lazy, primes, s, asm_inv, 0, qbits, share_np, lazy_out); break;
+        case 14: launch_it<14, SQ>(op, extP, T, blocks, L, K, lazy, primes, s); break;
         default: break;
     }
+}
+
+void launch_inv_tensor(const Operands& op, const u64* extP, u64* T, int items, int logn, int L, int K, bool lazy,
+                       const PrimeConst* primes, hipStream_t s, bool asm_inv, bool p2only, int qbits, int share_np,
+                       bool lazy_out, bool fold, bool square) {
+    if (square)
+        launch_inv_tensor_t<true>(op, extP, T, items, logn, L, K, lazy, primes, s, asm_inv, p2only, qbits, share_np,
+                                  lazy_out, fold);
+    else
+        launch_inv_tensor_t<false>(op, extP, T, items, logn, L, K, lazy, primes, s, asm_inv, p2only, qbits, share_np,
+                                   lazy_out, fold);
 }
 
 bool launch_ntt_fwd2(const NttBatch& nb1, int count1, const NttBatch& nb2, int count2, int logn,

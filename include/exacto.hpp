@@ -218,6 +218,36 @@ inline std::vector<BfvCiphertext> bfv_mul_and_relin(const std::vector<BfvCiphert
     return detail::unflatten(out, a.size(), 2, prm);
 }
 
+// Squares (exacto_bfv_square_*): bit for bit bfv_mul_no_relin(a, a) / bfv_mul_and_relin(a, a, rlk), the
+// operand's input work done once.
+inline std::vector<BfvCiphertext> bfv_square_no_relin(const std::vector<BfvCiphertext>& a) {
+    if (a.empty()) return {};
+    const BfvParamsPtr& prm = a[0].params;
+    const size_t p1 = a[0].c.size();
+    auto fa = detail::flatten(a, p1);
+    std::vector<uint64_t> out(a.size() * 3 * prm->num_limbs() * prm->ring_degree);
+    detail::check(exacto_bfv_square_no_relin(prm->ctx(), fa.data(), p1, out.data(), a.size()));
+    return detail::unflatten(out, a.size(), 3, prm);
+}
+
+inline std::vector<BfvCiphertext> bfv_square_and_relin(const std::vector<BfvCiphertext>& a, const RelinKey& rlk) {
+    if (a.empty()) return {};
+    const BfvParamsPtr& prm = a[0].params;
+    if (a[0].c.size() != 2) throw ExactoError(1, "invalid parameter: multiplication requires degree-1 ciphertexts");
+    detail::load_key(rlk);
+    auto fa = detail::flatten(a, 2);
+    std::vector<uint64_t> out(fa.size());
+    detail::check(exacto_bfv_square_and_relin(prm->ctx(), fa.data(), out.data(), a.size()));
+    return detail::unflatten(out, a.size(), 2, prm);
+}
+
+inline BfvCiphertext bfv_square_no_relin(const BfvCiphertext& a) {
+    return bfv_square_no_relin(std::vector<BfvCiphertext>{a})[0];
+}
+inline BfvCiphertext bfv_square_and_relin(const BfvCiphertext& a, const RelinKey& rlk) {
+    return bfv_square_and_relin(std::vector<BfvCiphertext>{a}, rlk)[0];
+}
+
 inline BfvCiphertext bfv_mul_no_relin(const BfvCiphertext& a, const BfvCiphertext& b) {
     return bfv_mul_no_relin(std::vector<BfvCiphertext>{a}, std::vector<BfvCiphertext>{b})[0];
 }
@@ -736,6 +766,40 @@ inline std::vector<DbfvCiphertext> dbfv_mul(const std::vector<DbfvCiphertext>& a
 
 inline DbfvCiphertext dbfv_mul(const DbfvCiphertext& a, const DbfvCiphertext& b, const RelinKey& rlk) {
     return dbfv_mul(std::vector<DbfvCiphertext>{a}, std::vector<DbfvCiphertext>{b}, rlk)[0];
+}
+
+// dbfv_mul(a, a, rlk) (exacto_dbfv_square): d (d + 1) / 2 of the d^2 digit-pair products, bit for bit.
+inline std::vector<DbfvCiphertext> dbfv_square(const std::vector<DbfvCiphertext>& a, const RelinKey& rlk) {
+    if (a.empty()) return {};
+    const auto& dp = *a[0].params;
+    const size_t d = dp.num_digits;
+    for (size_t i = 0; i < a.size(); ++i)
+        if (a[i].num_limbs() != d) throw ExactoError(1, "invalid parameter: multiplication requires d-limb ciphertexts");
+    detail::load_key(rlk);
+    std::vector<uint64_t> fa;
+    std::vector<uint32_t> da, dout(a.size());
+    for (size_t i = 0; i < a.size(); ++i) {
+        auto x = detail::flatten(a[i].limbs, 2);
+        fa.insert(fa.end(), x.begin(), x.end());
+        da.push_back((uint32_t)a[i].mul_depth);
+    }
+    std::vector<uint64_t> out(fa.size());
+    detail::check(exacto_dbfv_square(dp.bfv_params->ctx(), d, dp.base, dp.plain_modulus, fa.data(), out.data(), a.size(),
+                                     da.data(), dout.data()));
+    std::vector<DbfvCiphertext> res(a.size());
+    const size_t per = d * 2 * dp.bfv_params->num_limbs() * dp.bfv_params->ring_degree;
+    for (size_t i = 0; i < a.size(); ++i) {
+        std::vector<uint64_t> slice(out.begin() + (long)(i * per), out.begin() + (long)((i + 1) * per));
+        res[i].limbs = detail::unflatten(slice, d, 2, dp.bfv_params);
+        res[i].degree = d;
+        res[i].mul_depth = dout[i];
+        res[i].params = a[0].params;
+    }
+    return res;
+}
+
+inline DbfvCiphertext dbfv_square(const DbfvCiphertext& a, const RelinKey& rlk) {
+    return dbfv_square(std::vector<DbfvCiphertext>{a}, rlk)[0];
 }
 
 namespace detail {

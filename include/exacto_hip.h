@@ -183,6 +183,20 @@ int exacto_bfv_mul_and_relin(exacto_ctx* ctx, const uint64_t* ct1, const uint64_
 int exacto_bfv_mul_and_relin_dev(exacto_ctx* ctx, const uint64_t* ct1, const uint64_t* ct2,
                                  uint64_t* out, size_t batch);
 
+/* Squares: a ciphertext times itself on a one-operand pipeline (the input transformed, lifted and
+ * forward-transformed once instead of twice; the tensor loads each polynomial once and forms c1 as one
+ * doubled product).  Bit for bit exacto_bfv_mul_no_relin(ct, polys, ct, polys) and
+ * exacto_bfv_mul_and_relin(ct, ct), on every multiplication path, with the same error codes and
+ * messages (polys != 2, no key, a deferred parameter error).  ct = [B][2][L][n]; out = [B][3][L][n]
+ * (no_relin) or [B][2][L][n]; out must not overlap ct (InvalidParam); batch == 0 returns 0. */
+int exacto_bfv_square_no_relin(exacto_ctx* ctx, const uint64_t* ct, size_t polys, uint64_t* out, size_t batch);
+int exacto_bfv_square_no_relin_dev(exacto_ctx* ctx, const uint64_t* ct, size_t polys, uint64_t* out, size_t batch);
+int exacto_bfv_square_and_relin(exacto_ctx* ctx, const uint64_t* ct, uint64_t* out, size_t batch);
+int exacto_bfv_square_and_relin_dev(exacto_ctx* ctx, const uint64_t* ct, uint64_t* out, size_t batch);
+/* exacto_eval_poly's baby steps x^i = x^(i/2) x^(i/2) (even i) run exacto_bfv_square_and_relin_dev (the
+ * default, on != 0) or the two-operand call (on == 0: for A/B timing; the results are the same bits). */
+int exacto_ctx_set_square_hook(exacto_ctx* ctx, int on);
+
 /* gadget_decompose (keyswitch.rs:11-52) of coefficient-domain RNS polynomials [B][L][n]
  * (CRT value mod Q, extension semantics when Q >= 2^64) -> digits [B][G'][L][n] as
  * residues mod q_i, G' = min(G, num_digits). */
@@ -202,6 +216,26 @@ int exacto_dbfv_mul(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plai
 int exacto_dbfv_mul_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
                         const uint64_t* a, const uint64_t* b, uint64_t* out, size_t batch,
                         const uint32_t* depth_a, const uint32_t* depth_b, uint32_t* depth_out);
+
+/* dbfv_mul(a, a): a, out = [B][d][2][L][n], bit for bit exacto_dbfv_mul(a, a, depth_a, depth_a) with the
+ * same errors and depth_out.  The digit-pair products (i, j) and (j, i) are one ciphertext, so
+ * d (d + 1) / 2 of the d^2 products are formed and the operand is extended once; every output limb sums
+ * the same terms (a shared product counted for both of its ordered pairs), so the key switch taken
+ * (exacto_ctx_info.dbfv_key_switch) is the two-operand call's.  out must not overlap a. */
+int exacto_dbfv_square(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus, const uint64_t* a,
+                       uint64_t* out, size_t batch, const uint32_t* depth_a, uint32_t* depth_out);
+int exacto_dbfv_square_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus, const uint64_t* a,
+                           uint64_t* out, size_t batch, const uint32_t* depth_a, uint32_t* depth_out);
+
+/* The products and per-limb sums exacto_dbfv_mul (symmetric = 0) or exacto_dbfv_square (symmetric != 0)
+ * forms for the d output limbs, pure host code (no context): pairs = [npairs][2] digit indices (i, j) (the
+ * symmetric plan: i <= j only), term_start = [d + 1], terms = [nterms][2] = (index into pairs, coefficient),
+ * limb k summing terms term_start[k] .. term_start[k + 1] - 1.  *npairs / *nterms receive the counts; a
+ * NULL or too small pairs / terms buffer (capacities in entries) is left unwritten, term_start may be NULL.
+ * Errors: those of DbfvParams::new. */
+int exacto_dbfv_mul_plan(size_t d, uint64_t base, uint64_t dbfv_plain_modulus, int symmetric, int32_t* pairs,
+                         size_t pair_cap, size_t* npairs, int32_t* term_start, int64_t* terms, size_t term_cap,
+                         size_t* nterms);
 
 /* One GPU's share of a dbfv_mul whose d output limbs are split across GPUs (the d^2 digit-pair
  * products of dbfv/eval.rs:109-122 partitioned by output limb k = i + j, so no cross-GPU sum is
