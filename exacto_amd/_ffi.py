@@ -144,6 +144,18 @@ _SIGS = [
     ("exacto_gen_galois_key_dev", [_P, _P, _U64, C.c_double, _P, _U64, _SZ, _P], C.c_int),
     ("exacto_bfv_apply_automorphism", [_P, _P, _SZ, _U64, _P, _SZ, _P, _SZ], C.c_int),
     ("exacto_bfv_apply_automorphism_dev", [_P, _P, _SZ, _U64, _P, _SZ, _P, _SZ], C.c_int),
+    ("exacto_batch_info", [_P, C.POINTER(_U64)], C.c_int),
+    *[(f"exacto_batch_{op}{sfx}", [_P, _P, _P, _SZ], C.c_int) for op in ("encode", "decode") for sfx in ("", "_dev")],
+    ("exacto_galois_element_rotate_rows", [_SZ, C.c_int64, C.POINTER(_U64)], C.c_int),
+    ("exacto_galois_element_swap_rows", [_SZ, C.POINTER(_U64)], C.c_int),
+    ("exacto_bfv_rotate_rows", [_P, _P, _SZ, C.c_int64, _P, _SZ, _P, _SZ], C.c_int),
+    ("exacto_bfv_rotate_rows_dev", [_P, _P, _SZ, C.c_int64, _P, _SZ, _P, _SZ], C.c_int),
+    ("exacto_bfv_swap_rows", [_P, _P, _SZ, _P, _SZ, _P, _SZ], C.c_int),
+    ("exacto_bfv_swap_rows_dev", [_P, _P, _SZ, _P, _SZ, _P, _SZ], C.c_int),
+    *[(f"exacto_batch_encrypt_{kind}{sfx}", [_P, _P, _P, C.c_double, _P, _U64, _P, _SZ], C.c_int)
+      for kind in ("sk", "pk") for sfx in ("", "_dev")],
+    ("exacto_batch_decrypt", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
+    ("exacto_batch_decrypt_dev", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_plain_mul", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_plain_mul_dev", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_plain_add", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
@@ -298,6 +310,21 @@ def required_trace_elements(n: int) -> list[int]:
     out = (C.c_uint64 * max(count, 1))()
     lib.exacto_required_trace_elements(n, out, count)
     return [int(v) for v in out[:count]]
+
+
+def galois_element_rotate_rows(n: int, steps: int) -> int:
+    """3^(steps mod n/2) mod 2n: the element whose automorphism rotates both slot rows left by `steps`
+    (negative: right); host-only entry point."""
+    el = C.c_uint64(0)
+    check(load().exacto_galois_element_rotate_rows(n, steps, C.byref(el)))
+    return int(el.value)
+
+
+def galois_element_swap_rows(n: int) -> int:
+    """2n - 1: the element whose automorphism exchanges the two slot rows; host-only entry point."""
+    el = C.c_uint64(0)
+    check(load().exacto_galois_element_swap_rows(n, C.byref(el)))
+    return int(el.value)
 
 
 def dbfv_change_base_matrix(d: int, base: int, plain: int, new_base: int, new_d: int) -> np.ndarray:
@@ -770,6 +797,102 @@ class HipContext:
 
     def required_trace_elements(self, n=None) -> list[int]:
         return required_trace_elements(self.n if n is None else n)
+
+    # ---- SIMD batching (exacto_batch_*): slot vectors [B][n] as 2 x n/2 matrices, exacto_hip.h
+    def batch_info(self) -> int:
+        """zeta of the slot encoding; raises the context's batching error when it cannot batch."""
+        root = C.c_uint64(0)
+        check(self._lib.exacto_batch_info(self._h, C.byref(root)))
+        return int(root.value)
+
+    def _batch_rows(self, a, what):
+        a = _u64(a)
+        if a.ndim != 2 or a.shape[1] != self.n:
+            raise ValueError(f"{what} must be a [B][{self.n}] array")
+        return a
+
+    def batch_encode(self, values) -> np.ndarray:
+        """values [B][n] (each below t, else InvalidParam) -> plaintext coefficients [B][n]."""
+        v = self._batch_rows(values, "values")
+        pt = np.zeros_like(v)
+        check(self._lib.exacto_batch_encode(self._h, v.ctypes.data, pt.ctypes.data, v.shape[0]))
+        return pt
+
+    def batch_decode(self, pt) -> np.ndarray:
+        """plaintext coefficients [B][n] (reduced mod t) -> values [B][n]."""
+        p = self._batch_rows(pt, "pt")
+        v = np.zeros_like(p)
+        check(self._lib.exacto_batch_decode(self._h, p.ctypes.data, v.ctypes.data, p.shape[0]))
+        return v
+
+    def rotate_rows(self, ct, steps, gk=None) -> np.ndarray:
+        """Both slot rows left by `steps`: bfv_apply_automorphism with 3^steps mod 2n and its key gk
+        (None allowed when steps == 0 mod n/2)."""
+        ct = _u64(ct)
+        gk = None if gk is None else _u64(gk)
+        out = np.zeros((ct.shape[0], ct.shape[1], self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_bfv_rotate_rows(self._h, ct.ctypes.data, ct.shape[1], int(steps),
+                                               gk.ctypes.data if gk is not None and gk.size else None,
+                                               0 if gk is None else gk.shape[0], out.ctypes.data, ct.shape[0]))
+        return out
+
+    def swap_rows(self, ct, gk) -> np.ndarray:
+        """The two slot rows exchanged: bfv_apply_automorphism with 2n - 1 and its key gk."""
+        ct, gk = _u64(ct), _u64(gk)
+        out = np.zeros((ct.shape[0], ct.shape[1], self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_bfv_swap_rows(self._h, ct.ctypes.data, ct.shape[1], gk.ctypes.data if gk.size else None,
+                                             gk.shape[0], out.ctypes.data, ct.shape[0]))
+        return out
+
+    def batch_encrypt_sk(self, values, sk, key, stream=0, sigma=3.2) -> np.ndarray:
+        """batch_encode then encrypt_sk on the device: values [B][n] -> ct [B][2][L][n]."""
+        k, v, sk = self._key(key), self._batch_rows(values, "values"), _u64(sk)
+        ct = np.zeros((v.shape[0], 2, self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_batch_encrypt_sk(self._h, v.ctypes.data, sk.ctypes.data, sigma, k.ctypes.data, stream,
+                                                ct.ctypes.data, v.shape[0]))
+        return ct
+
+    def batch_encrypt_pk(self, values, pk, key, stream=0, sigma=3.2) -> np.ndarray:
+        k, v, pk = self._key(key), self._batch_rows(values, "values"), _u64(pk)
+        ct = np.zeros((v.shape[0], 2, self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_batch_encrypt_pk(self._h, v.ctypes.data, pk.ctypes.data, sigma, k.ctypes.data, stream,
+                                                ct.ctypes.data, v.shape[0]))
+        return ct
+
+    def batch_decrypt(self, ct, sk) -> np.ndarray:
+        """bfv_decrypt then batch_decode on the device: ct [B][polys][L][n] -> values [B][n]."""
+        ct, sk = _u64(ct), _u64(sk)
+        out = np.zeros((ct.shape[0], self.n), dtype=np.uint64)
+        check(self._lib.exacto_batch_decrypt(self._h, ct.ctypes.data, ct.shape[1], sk.ctypes.data, out.ctypes.data,
+                                             ct.shape[0]))
+        return out
+
+    def batch_encode_dev(self, values, pt, batch):
+        """Device form: every value is reduced mod t (no range error); pt may be values (in place)."""
+        check(self._lib.exacto_batch_encode_dev(self._h, self._p(values), self._p(pt), batch))
+
+    def batch_decode_dev(self, pt, values, batch):
+        check(self._lib.exacto_batch_decode_dev(self._h, self._p(pt), self._p(values), batch))
+
+    def rotate_rows_dev(self, ct, steps, gk, num_keys, out, batch):
+        check(self._lib.exacto_bfv_rotate_rows_dev(self._h, self._p(ct), 2, int(steps), self._p(gk), num_keys,
+                                                   self._p(out), batch))
+
+    def swap_rows_dev(self, ct, gk, num_keys, out, batch):
+        check(self._lib.exacto_bfv_swap_rows_dev(self._h, self._p(ct), 2, self._p(gk), num_keys, self._p(out), batch))
+
+    def batch_encrypt_sk_dev(self, values, sk, key, stream, ct, batch, sigma=3.2):
+        k = self._key(key)
+        check(self._lib.exacto_batch_encrypt_sk_dev(self._h, self._p(values), self._p(sk), sigma, k.ctypes.data, stream,
+                                                    self._p(ct), batch))
+
+    def batch_encrypt_pk_dev(self, values, pk, key, stream, ct, batch, sigma=3.2):
+        k = self._key(key)
+        check(self._lib.exacto_batch_encrypt_pk_dev(self._h, self._p(values), self._p(pk), sigma, k.ctypes.data, stream,
+                                                    self._p(ct), batch))
+
+    def batch_decrypt_dev(self, ct, polys, sk, values, batch):
+        check(self._lib.exacto_batch_decrypt_dev(self._h, self._p(ct), polys, self._p(sk), self._p(values), batch))
 
     def gen_trace_galois_keys(self, sk, key, stream=0, elements=None, sigma=3.2):
         """gen_trace_galois_keys / gen_all_galois_keys (coeffs_to_slots.rs:151-197): one key per element,

@@ -394,6 +394,17 @@ struct exacto_ctx {
     std::vector<u64> msw_w, msw_ws;
     u64* msw_buf = nullptr;
     size_t msw_cap = 0;
+    // SIMD batching (batch.hip): validated and built at the context's first batching call (batch_ready)
+    int batch_state = 0;             // 0: not tried, 1: tables resident, -1: this context cannot batch
+    int batch_code = 0;              // ... and why
+    std::string batch_msg;
+    u64 batch_root = 0;              // zeta = find_psi(n, t)
+    int batch_form = 0;              // the transforms' arithmetic (F32_LAZY / F32_WIDE / BF_STRICT)
+    BatchTab batch_tab{};
+    uint2* d_btw = nullptr;          // [2][n] forward, inverse twiddles mod t
+    uint32_t* d_bperm = nullptr;     // [n] slot -> storage position
+    u64* batch_buf = nullptr;        // the compositions' plaintexts, one chunk
+    size_t batch_cap = 0;
     size_t cached_B = 0, cached_d = 0;
     u64 cached_base = 0, cached_p = 0;
     int cached_npairs = 0;
@@ -1193,6 +1204,7 @@ extern "C" void exacto_ctx_destroy(exacto_ctx* c) {
     if (c->ev_twin_in) (void)hipEventDestroy(c->ev_twin_in);
     free_dev(c->io); free_dev(c->prod); free_dev(c->d_off); free_dev(c->d_term_start); free_dev(c->d_terms);
     free_dev(c->d_slot_start); free_dev(c->gsum_buf); free_dev(c->msw_buf);
+    free_dev(c->d_btw); free_dev(c->d_bperm); free_dev(c->batch_buf);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     free_dev(c->boot_buf); free_dev(c->boot_slots);
     delete c;
@@ -3482,8 +3494,11 @@ struct DbfvPlain {
 // dp != nullptr: pt holds B dBFV plaintexts and the batch is their B * d digit encryptions, ct =
 // [B][d][2][L][n]: item b * d + k is what this function gives for digit plaintext k of item b; only
 // Delta*m is produced differently (straight from pt, and already in the NTT domain for scalars).
+// item0: the batch is items item0 .. item0 + B - 1 of a larger call (their sample indices; the batch
+// compositions' chunks)
 static int encrypt_batch(exacto_ctx* c, const u64* pt, const u64* sk, const u64* pk, double sigma,
-                         const uint64_t* key, u64 stream, u64* ct, size_t B, const DbfvPlain* dp = nullptr) {
+                         const uint64_t* key, u64 stream, u64* ct, size_t B, const DbfvPlain* dp = nullptr,
+                         size_t item0 = 0) {
     if (!key || !pt || !ct || (!sk && !pk)) return invalid_param("null argument");
     const size_t items = dp ? B * dp->d : B;
     if (items == 0) return 0;
@@ -3506,16 +3521,16 @@ static int encrypt_batch(exacto_ctx* c, const u64* pt, const u64* sk, const u64*
         if (int e = ntt_items(c, dm, (long)items, Ln, c->L)) return e;
     if (!pk) {
         // encrypt.rs:79-106, item b: a (index 2b) -> c1, e (index 2b+1) -> c0 slot
-        if (int e = sample_polys(c, KG_UNIFORM, k, stream, ct + Ln, 2 * Ln, 0, 2, (long)items, sigma)) return e;
-        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct, 2 * Ln, 1, 2, (long)items, sigma)) return e;
+        if (int e = sample_polys(c, KG_UNIFORM, k, stream, ct + Ln, 2 * Ln, 2 * item0, 2, (long)items, sigma)) return e;
+        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct, 2 * Ln, 2 * item0 + 1, 2, (long)items, sigma)) return e;
         if (int e = ntt_items(c, ct, (long)items, 2 * Ln, 2L * c->L)) return e;
         launch_combine(KG_ENC_SK, ct, (long)items, 2 * Ln, Ln, sk, dm, nullptr, nullptr, nullptr, c->n, c->L,
                        c->d_primes, c->stream);
     } else {
         // encrypt.rs:29-69, item b: u binary (3b), e1 (3b+1) -> c0 slot, e2 (3b+2) -> c1 slot
-        if (int e = sample_polys(c, KG_BINARY, k, stream, u, Ln, 0, 3, (long)items, sigma)) return e;
-        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct, 2 * Ln, 1, 3, (long)items, sigma)) return e;
-        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct + Ln, 2 * Ln, 2, 3, (long)items, sigma)) return e;
+        if (int e = sample_polys(c, KG_BINARY, k, stream, u, Ln, 3 * item0, 3, (long)items, sigma)) return e;
+        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct, 2 * Ln, 3 * item0 + 1, 3, (long)items, sigma)) return e;
+        if (int e = sample_polys(c, KG_GAUSSIAN, k, stream, ct + Ln, 2 * Ln, 3 * item0 + 2, 3, (long)items, sigma)) return e;
         if (int e = ntt_items(c, u, (long)items, Ln, c->L)) return e;
         if (int e = ntt_items(c, ct, (long)items, 2 * Ln, 2L * c->L)) return e;
         launch_combine(KG_ENC_PK, ct, (long)items, 2 * Ln, Ln, nullptr, u, dm, pk, nullptr, c->n, c->L, c->d_primes,
@@ -4473,6 +4488,278 @@ extern "C" int exacto_encrypt_pk(exacto_ctx* c, const uint64_t* pt, const uint64
                      [&](std::vector<u64*>& d, u64* o) {
                          return exacto_encrypt_pk_dev(c, d[0], d[1], sigma, key, stream, o, B);
                      });
+}
+
+// ============================================================== SIMD batching (replaces bfv/encoding.rs)
+// Slot encode / decode mod t (batch.hip), row rotations and the encode + encrypt / decrypt + decode
+// compositions.  The convention is in include/exacto_hip.h.
+
+// The first batching call of a context validates (n, t) and builds the tables; a context that cannot
+// batch gives the same error at every batching call and is otherwise untouched.
+static int batch_ready(exacto_ctx* c) {
+    if (c->batch_state == 1) return 0;
+    if (c->batch_state < 0) return fail(c->batch_code, c->batch_msg);
+    const u64 t = c->plain;
+    const int n = c->n, logn = c->logn;
+    auto cannot = [&](int code, const std::string& msg) {
+        c->batch_state = -1;
+        c->batch_code = code;
+        c->batch_msg = msg;
+        return fail(code, msg);
+    };
+    if (n < 16 || n > 16384 || t < 2 || (t - 1) % (2 * (u64)n) != 0 || !is_prime_h(t))
+        return cannot(EXACTO_ERR_INVALID_PARAM,
+                      "invalid parameter: batching requires a prime plaintext modulus t ≡ 1 (mod 2n), got t=" +
+                          std::to_string(t) + ", n=" + std::to_string(n));
+    if (t >= (1ull << 32))
+        return cannot(EXACTO_ERR_NOT_IMPLEMENTED, "not yet implemented: batching for plaintext moduli >= 2^32");
+    const u64 zeta = find_psi((u64)n, t), zeta_inv = invmod_h(zeta, t);
+    auto sh32 = [](u64 w, u64 p) { return (uint32_t)((w << 32) / p); };
+    std::vector<uint2> tw((size_t)2 * n);
+    for (int i = 0; i < n; ++i) {
+        const int e = bitrev(i, logn);
+        const u64 w = powmod_h(zeta, e, t), wi = powmod_h(zeta_inv, e, t);
+        tw[i] = make_uint2((uint32_t)w, sh32(w, t));
+        tw[(size_t)n + i] = make_uint2((uint32_t)wi, sh32(wi, t));
+    }
+    // slot i of row 0 is exponent 3^i, of row 1 exponent 2n - 3^i; exponent e is evaluation brv((e - 1) / 2)
+    std::vector<uint32_t> perm(n);
+    const int T = n / 16;
+    u64 e = 1;
+    for (int i = 0; i < n / 2; ++i) {
+        const int k0 = bitrev((int)((e - 1) / 2), logn), k1 = bitrev((int)((2 * (u64)n - e - 1) / 2), logn);
+        perm[i] = (uint32_t)((k0 % 16) * T + k0 / 16);
+        perm[n / 2 + i] = (uint32_t)((k1 % 16) * T + k1 / 16);
+        e = e * 3 % (2 * (u64)n);
+    }
+    if (!c->d_btw) HIP_TRY(dev_alloc((void**)&c->d_btw, tw.size() * sizeof(uint2)));
+    if (!c->d_bperm) HIP_TRY(dev_alloc((void**)&c->d_bperm, perm.size() * sizeof(uint32_t)));
+    if (int e_ = upload(c, c->d_btw, tw.data(), tw.size() * sizeof(uint2))) return e_;
+    if (int e_ = upload(c, c->d_bperm, perm.data(), perm.size() * sizeof(uint32_t))) return e_;
+    BatchTab& B = c->batch_tab;
+    std::memset(&B, 0, sizeof(B));
+    const u64 ninv = invmod_h((u64)n % t, t), lw = mulmod_h(tw[(size_t)n + 1].x, ninv, t);
+    B.P.p = (uint32_t)t;
+    B.P.n_inv = (uint32_t)ninv;
+    B.P.n_inv_s = sh32(ninv, t);
+    B.P.last_w = (uint32_t)lw;
+    B.P.last_ws = sh32(lw, t);
+    B.P.tw_fwd = c->d_btw;
+    B.P.tw_inv = c->d_btw + n;
+    B.mu = ~0ull / t;
+    B.perm = c->d_bperm;
+    // ks32_dev.hpp's forms: lazy butterflies below 2^30 (2), reduced operands below 2^31 (0); beyond, 64-bit carries
+    c->batch_form = t < (1ull << 30) ? 2 : t < (1ull << 31) ? 0 : BF_STRICT;
+    c->batch_root = zeta;
+    c->batch_state = 1;
+    return 0;
+}
+
+extern "C" int exacto_batch_info(exacto_ctx* c, uint64_t* root) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = batch_ready(c)) return e;
+    if (root) *root = c->batch_root;
+    return 0;
+}
+
+// in / out [B][n]: equal or disjoint
+static int batch_overlap_check(const uint64_t* in, const uint64_t* out, size_t words) {
+    if (!in || !out) return invalid_param("batch: null buffer");
+    if (in != out && out < in + words && in < out + words)
+        return invalid_param("batch: out overlaps in (only out == in is allowed)");
+    return 0;
+}
+
+static int batch_transform_dev(exacto_ctx* c, bool encode, const uint64_t* in, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = batch_ready(c)) return e;
+    if (B == 0) return 0;
+    if (int e = batch_overlap_check(in, out, B * (size_t)c->n)) return e;
+    if (((uintptr_t)in | (uintptr_t)out) & 15) return invalid_param("batch: buffers must be 16-byte aligned");
+    // one grid dimension: 2^31 - 1 polynomials per launch
+    const size_t step = (size_t)1 << 30;
+    for (size_t i0 = 0; i0 < B; i0 += step) {
+        launch_batch_transform(encode, in + i0 * c->n, out + i0 * c->n, (long)std::min(step, B - i0), c->logn,
+                               c->batch_tab, c->batch_form, c->stream);
+        CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+extern "C" int exacto_batch_encode_dev(exacto_ctx* c, const uint64_t* values, uint64_t* pt, size_t B) {
+    return batch_transform_dev(c, true, values, pt, B);
+}
+extern "C" int exacto_batch_decode_dev(exacto_ctx* c, const uint64_t* pt, uint64_t* values, size_t B) {
+    return batch_transform_dev(c, false, pt, values, B);
+}
+
+// encode_simd's range check (encoding.rs:40-46): the first value >= t
+static int batch_values_check(const exacto_ctx* c, const uint64_t* values, size_t B) {
+    for (size_t i = 0; i < B * (size_t)c->n; ++i)
+        if (values[i] >= c->plain)
+            return invalid_param("plaintext " + std::to_string(values[i]) + " >= plain_modulus " +
+                                 std::to_string(c->plain));
+    return 0;
+}
+
+static int batch_transform_host(exacto_ctx* c, bool encode, const uint64_t* in, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = batch_ready(c)) return e;
+    if (B == 0) return 0;
+    if (int e = batch_overlap_check(in, out, B * (size_t)c->n)) return e;
+    if (encode)
+        if (int e = batch_values_check(c, in, B)) return e;
+    const size_t bytes = B * poly_bytes(c);
+    return host_call(c, {{in, bytes}}, bytes, out,
+                     [&](std::vector<u64*>& d, u64* o) { return batch_transform_dev(c, encode, d[0], o, B); });
+}
+
+extern "C" int exacto_batch_encode(exacto_ctx* c, const uint64_t* values, uint64_t* pt, size_t B) {
+    return batch_transform_host(c, true, values, pt, B);
+}
+extern "C" int exacto_batch_decode(exacto_ctx* c, const uint64_t* pt, uint64_t* values, size_t B) {
+    return batch_transform_host(c, false, pt, values, B);
+}
+
+// 3^(steps mod n/2) mod 2n (negative steps rotate right) and 2n - 1; host only
+extern "C" int exacto_galois_element_rotate_rows(size_t n, int64_t steps, uint64_t* element) {
+    if (!element) return invalid_param("null argument");
+    if (n < 4 || (n & (n - 1)) != 0) return fail(EXACTO_ERR_INVALID_RING_DEGREE,
+                                                 "ring degree must be a power of 2, got " + std::to_string(n));
+    const int64_t h = (int64_t)(n / 2);
+    const uint64_t k = (uint64_t)(((steps % h) + h) % h);
+    *element = powmod_h(3, k, 2 * (u64)n);
+    return 0;
+}
+extern "C" int exacto_galois_element_swap_rows(size_t n, uint64_t* element) {
+    if (!element) return invalid_param("null argument");
+    if (n < 4 || (n & (n - 1)) != 0) return fail(EXACTO_ERR_INVALID_RING_DEGREE,
+                                                 "ring degree must be a power of 2, got " + std::to_string(n));
+    *element = 2 * (u64)n - 1;
+    return 0;
+}
+
+extern "C" int exacto_bfv_rotate_rows_dev(exacto_ctx* c, const uint64_t* ct, size_t polys, int64_t steps,
+                                          const uint64_t* gk, size_t num_keys, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    uint64_t element = 1;
+    if (int e = exacto_galois_element_rotate_rows((size_t)c->n, steps, &element)) return e;
+    if (element != 1) return exacto_bfv_apply_automorphism_dev(c, ct, polys, element, gk, num_keys, out, B);
+    // the identity: a copy, no key
+    if (polys != 2) return invalid_param("automorphism requires degree-1 ciphertext");
+    if (B == 0) return 0;
+    if (!ct || !out) return invalid_param("null argument");
+    if (out != ct) HIP_TRY(dev_copy(out, ct, B * 2 * c->L * poly_bytes(c), c->stream));
+    return 0;
+}
+extern "C" int exacto_bfv_swap_rows_dev(exacto_ctx* c, const uint64_t* ct, size_t polys, const uint64_t* gk,
+                                        size_t num_keys, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    return exacto_bfv_apply_automorphism_dev(c, ct, polys, 2 * (u64)c->n - 1, gk, num_keys, out, B);
+}
+extern "C" int exacto_bfv_rotate_rows(exacto_ctx* c, const uint64_t* ct, size_t polys, int64_t steps,
+                                      const uint64_t* gk, size_t num_keys, uint64_t* out, size_t B) {
+    if (!c) return invalid_param("null context");
+    uint64_t element = 1;
+    if (int e = exacto_galois_element_rotate_rows((size_t)c->n, steps, &element)) return e;
+    if (element != 1) return exacto_bfv_apply_automorphism(c, ct, polys, element, gk, num_keys, out, B);
+    if (polys != 2) return invalid_param("automorphism requires degree-1 ciphertext");
+    if (B == 0) return 0;
+    if (!ct || !out) return invalid_param("null argument");
+    if (out != ct) std::memmove(out, ct, B * 2 * c->L * poly_bytes(c));
+    return 0;
+}
+extern "C" int exacto_bfv_swap_rows(exacto_ctx* c, const uint64_t* ct, size_t polys, const uint64_t* gk,
+                                    size_t num_keys, uint64_t* out, size_t B) {
+    if (!c) return invalid_param("null context");
+    return exacto_bfv_apply_automorphism(c, ct, polys, 2 * (u64)c->n - 1, gk, num_keys, out, B);
+}
+
+// encode + encrypt chunk by chunk through batch_buf: the chunk's items keep the sample indices they
+// have in one exacto_encrypt_* call over the whole batch, so the ciphertexts are that call's bit for bit
+static int batch_encrypt_dev(exacto_ctx* c, const uint64_t* values, const uint64_t* sk, const uint64_t* pk,
+                             double sigma, const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = batch_ready(c)) return e;
+    if (!key || !values || !ct || (!sk && !pk)) return invalid_param("null argument");
+    if (B == 0) return 0;
+    if ((uintptr_t)values & 15) return invalid_param("batch: buffers must be 16-byte aligned");
+    const size_t C = std::min<size_t>(c->chunk, B), n = (size_t)c->n;
+    if (grow(&c->batch_buf, &c->batch_cap, C * poly_bytes(c))) return EXACTO_ERR_HIP;
+    for (size_t i0 = 0; i0 < B; i0 += C) {
+        const size_t cnt = std::min(C, B - i0);
+        launch_batch_transform(true, values + i0 * n, c->batch_buf, (long)cnt, c->logn, c->batch_tab, c->batch_form,
+                               c->stream);
+        CHECK_LAUNCH();
+        if (int e = encrypt_batch(c, c->batch_buf, sk, pk, sigma, key, stream, ct + i0 * 2 * c->L * n, cnt, nullptr, i0))
+            return e;
+    }
+    return 0;
+}
+
+extern "C" int exacto_batch_encrypt_sk_dev(exacto_ctx* c, const uint64_t* values, const uint64_t* sk, double sigma,
+                                           const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (c && !sk) return invalid_param("null argument");
+    return batch_encrypt_dev(c, values, sk, nullptr, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_batch_encrypt_pk_dev(exacto_ctx* c, const uint64_t* values, const uint64_t* pk, double sigma,
+                                           const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (c && !pk) return invalid_param("null argument");
+    return batch_encrypt_dev(c, values, nullptr, pk, sigma, key, stream, ct, B);
+}
+
+extern "C" int exacto_batch_decrypt_dev(exacto_ctx* c, const uint64_t* ct, size_t polys, const uint64_t* sk,
+                                        uint64_t* values, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = batch_ready(c)) return e;
+    if (polys < 1) return invalid_param("ciphertext has no polynomials");
+    if (B == 0) return 0;
+    if (!ct || !sk || !values) return invalid_param("null argument");
+    if ((uintptr_t)values & 15) return invalid_param("batch: buffers must be 16-byte aligned");
+    const size_t C = std::min<size_t>(c->chunk, B), n = (size_t)c->n;
+    const long stride = (long)polys * c->L * c->n;
+    if (grow(&c->batch_buf, &c->batch_cap, C * poly_bytes(c))) return EXACTO_ERR_HIP;
+    for (size_t i0 = 0; i0 < B; i0 += C) {
+        const size_t cnt = std::min(C, B - i0);
+        if (int e = decrypt_batch(c, ct + i0 * (size_t)stride, polys, stride, sk, c->batch_buf, cnt)) return e;
+        launch_batch_transform(false, c->batch_buf, values + i0 * n, (long)cnt, c->logn, c->batch_tab, c->batch_form,
+                               c->stream);
+        CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+extern "C" int exacto_batch_encrypt_sk(exacto_ctx* c, const uint64_t* values, const uint64_t* sk, double sigma,
+                                       const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = batch_ready(c)) return e;
+    if (!values || !sk || !ct) return invalid_param("null argument");
+    if (int e = batch_values_check(c, values, B)) return e;
+    return host_call(c, {{values, B * poly_bytes(c)}, {sk, c->L * poly_bytes(c)}}, B * 2 * c->L * poly_bytes(c), ct,
+                     [&](std::vector<u64*>& d, u64* o) {
+                         return exacto_batch_encrypt_sk_dev(c, d[0], d[1], sigma, key, stream, o, B);
+                     });
+}
+extern "C" int exacto_batch_encrypt_pk(exacto_ctx* c, const uint64_t* values, const uint64_t* pk, double sigma,
+                                       const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = batch_ready(c)) return e;
+    if (!values || !pk || !ct) return invalid_param("null argument");
+    if (int e = batch_values_check(c, values, B)) return e;
+    return host_call(c, {{values, B * poly_bytes(c)}, {pk, 2 * c->L * poly_bytes(c)}}, B * 2 * c->L * poly_bytes(c), ct,
+                     [&](std::vector<u64*>& d, u64* o) {
+                         return exacto_batch_encrypt_pk_dev(c, d[0], d[1], sigma, key, stream, o, B);
+                     });
+}
+extern "C" int exacto_batch_decrypt(exacto_ctx* c, const uint64_t* ct, size_t polys, const uint64_t* sk,
+                                    uint64_t* values, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = batch_ready(c)) return e;
+    if (polys < 1) return invalid_param("ciphertext has no polynomials");
+    if (B == 0) return 0;
+    if (!ct || !sk || !values) return invalid_param("null argument");
+    return host_call(c, {{ct, B * polys * c->L * poly_bytes(c)}, {sk, c->L * poly_bytes(c)}}, B * poly_bytes(c), values,
+                     [&](std::vector<u64*>& dv, u64* o) { return exacto_batch_decrypt_dev(c, dv[0], polys, dv[1], o, B); });
 }
 
 // ============================================================== dBFV beyond the product

@@ -152,6 +152,23 @@ void ks32_mac(const uint32_t* DS, const uint32_t* RS, uint32_t* U, int items, in
 void ks32_crt(const uint32_t* U, u64* R, long r_stride, int items, int L, int S, int logn, const Ks32Tables* KT,
               const Prime32* primes, const PrimeConst* qprimes, int form, hipStream_t st, bool fpc = false);
 
+// ---- batch.hip: slot encode / decode modulo the plaintext prime t < 2^32 ----
+// P: t with its twiddles {zeta^brv(i), Shoup} / {zeta^-brv(i), Shoup}, n^-1 and last_w (the ks32 fields
+// beyond those are unused); mu = floor((2^64 - 1) / t); perm[slot] = storage position of the slot's
+// evaluation ((k mod 16) n/16 + k / 16 with k = brv((e - 1) / 2), e the slot's exponent)
+struct BatchTab {
+    Prime32 P;
+    u64 mu;
+    const uint32_t* perm;
+};
+// the transforms' arithmetic next to ks32_dev.hpp's F32_WIDE (0) and F32_LAZY (2): t in [2^31, 2^32)
+enum { BF_STRICT = 3 };
+// encode: values [count][n] -> coefficients (inverse transform, n^-1); otherwise coefficients -> values.
+// Inputs are any u64 (reduced mod t in the kernel); out == in allowed, no other overlap.
+// form: F32_LAZY (t < 2^30), F32_WIDE (t < 2^31) or BF_STRICT; 4 <= logn <= 14
+void launch_batch_transform(bool encode, const u64* in, u64* out, long count, int logn, const BatchTab& tab, int form,
+                            hipStream_t s);
+
 // ---- kernels.hip launchers (all asynchronous on `s`) ----
 struct Operands {            // two degree-1 ciphertext sources, [2][L][n] per item
     const u64* a;

@@ -492,6 +492,157 @@ inline CoeffPoly encode_scalar(uint64_t m, const BfvParamsPtr& prm) {
 }
 inline uint64_t decode_scalar(const CoeffPoly& p) { return p.coeffs.empty() ? 0 : p.coeffs[0]; }
 
+// ---- SIMD batching (replaces src/bfv/encoding.rs encode_simd / decode_simd, which pack coefficients):
+// slot vectors of n values as 2 x n/2 matrices, the convention of include/exacto_hip.h.  Needs a prime
+// plain_modulus == 1 (mod 2n) below 2^32; a context that cannot batch throws at its first batching call.
+using SlotVector = std::vector<uint64_t>;
+
+// zeta of the slot encoding (exacto_batch_info)
+inline uint64_t batch_root(const BfvParamsPtr& prm) {
+    uint64_t root = 0;
+    detail::check(exacto_batch_info(prm->ctx(), &root));
+    return root;
+}
+namespace detail {
+inline std::vector<uint64_t> flatten_slots(const std::vector<SlotVector>& values, size_t n) {
+    std::vector<uint64_t> out;
+    for (auto& v : values) {
+        if (v.size() != n) throw ExactoError(2, "dimension mismatch: expected " + std::to_string(n) + ", got " +
+                                                    std::to_string(v.size()));
+        out.insert(out.end(), v.begin(), v.end());
+    }
+    return out;
+}
+inline std::vector<SlotVector> split_slots(const std::vector<uint64_t>& flat, size_t batch, size_t n) {
+    std::vector<SlotVector> out(batch);
+    for (size_t b = 0; b < batch; ++b) out[b].assign(flat.begin() + (long)(b * n), flat.begin() + (long)((b + 1) * n));
+    return out;
+}
+inline std::vector<uint64_t> flatten_key(const std::vector<std::pair<RnsPoly, RnsPoly>>& keys) {
+    std::vector<uint64_t> key;
+    for (auto& k : keys) {
+        key.insert(key.end(), k.first.data.begin(), k.first.data.end());
+        key.insert(key.end(), k.second.data.begin(), k.second.data.end());
+    }
+    return key;
+}
+}  // namespace detail
+
+// values (each below t: InvalidParam "plaintext {v} >= plain_modulus {t}" otherwise) -> plaintexts
+inline std::vector<CoeffPoly> batch_encode(const std::vector<SlotVector>& values, const BfvParamsPtr& prm) {
+    const size_t n = prm->ring_degree;
+    auto flat = detail::flatten_slots(values, n);
+    std::vector<uint64_t> out(flat.size());
+    detail::check(exacto_batch_encode(prm->ctx(), flat.data(), out.data(), values.size()));
+    std::vector<CoeffPoly> res(values.size());
+    for (size_t b = 0; b < values.size(); ++b) {
+        res[b].coeffs.assign(out.begin() + (long)(b * n), out.begin() + (long)((b + 1) * n));
+        res[b].modulus = prm->plain_modulus;
+    }
+    return res;
+}
+inline CoeffPoly batch_encode(const SlotVector& values, const BfvParamsPtr& prm) {
+    return batch_encode(std::vector<SlotVector>{values}, prm)[0];
+}
+inline std::vector<SlotVector> batch_decode(const std::vector<CoeffPoly>& pts, const BfvParamsPtr& prm) {
+    const size_t n = prm->ring_degree;
+    std::vector<uint64_t> flat;
+    for (auto& p : pts) {
+        if (p.coeffs.size() != n) throw ExactoError(2, "dimension mismatch: expected " + std::to_string(n) +
+                                                           ", got " + std::to_string(p.coeffs.size()));
+        flat.insert(flat.end(), p.coeffs.begin(), p.coeffs.end());
+    }
+    std::vector<uint64_t> out(flat.size());
+    detail::check(exacto_batch_decode(prm->ctx(), flat.data(), out.data(), pts.size()));
+    return detail::split_slots(out, pts.size(), n);
+}
+inline SlotVector batch_decode(const CoeffPoly& pt, const BfvParamsPtr& prm) {
+    return batch_decode(std::vector<CoeffPoly>{pt}, prm)[0];
+}
+
+// 3^(steps mod n/2) mod 2n (negative steps rotate right) and 2n - 1: the keys to generate
+inline size_t galois_element_rotate_rows(size_t n, int64_t steps) {
+    uint64_t el = 0;
+    detail::check(exacto_galois_element_rotate_rows(n, steps, &el));
+    return (size_t)el;
+}
+inline size_t galois_element_swap_rows(size_t n) {
+    uint64_t el = 0;
+    detail::check(exacto_galois_element_swap_rows(n, &el));
+    return (size_t)el;
+}
+
+// both slot rows left by `steps`; gk is the key of galois_element_rotate_rows(n, steps), or nullptr
+// when steps == 0 (mod n/2), which copies
+inline std::vector<BfvCiphertext> bfv_rotate_rows(const std::vector<BfvCiphertext>& cts, int64_t steps,
+                                                  const GaloisKey* gk) {
+    if (cts.empty()) return {};
+    const BfvParams& prm = *cts[0].params;
+    const size_t polys = cts[0].c.size();
+    auto flat = detail::flatten(cts, polys);
+    std::vector<uint64_t> key;
+    if (gk) key = detail::flatten_key(gk->keys);
+    std::vector<uint64_t> out(flat.size());
+    detail::check(exacto_bfv_rotate_rows(prm.ctx(), flat.data(), polys, steps, key.empty() ? nullptr : key.data(),
+                                         gk ? gk->keys.size() : 0, out.data(), cts.size()));
+    return detail::unflatten(out, cts.size(), polys, cts[0].params);
+}
+inline BfvCiphertext bfv_rotate_rows(const BfvCiphertext& ct, int64_t steps, const GaloisKey& gk) {
+    return bfv_rotate_rows(std::vector<BfvCiphertext>{ct}, steps, &gk)[0];
+}
+inline std::vector<BfvCiphertext> bfv_swap_rows(const std::vector<BfvCiphertext>& cts, const GaloisKey& gk) {
+    if (cts.empty()) return {};
+    const BfvParams& prm = *cts[0].params;
+    const size_t polys = cts[0].c.size();
+    auto flat = detail::flatten(cts, polys);
+    auto key = detail::flatten_key(gk.keys);
+    std::vector<uint64_t> out(flat.size());
+    detail::check(exacto_bfv_swap_rows(prm.ctx(), flat.data(), polys, key.empty() ? nullptr : key.data(),
+                                       gk.keys.size(), out.data(), cts.size()));
+    return detail::unflatten(out, cts.size(), polys, cts[0].params);
+}
+inline BfvCiphertext bfv_swap_rows(const BfvCiphertext& ct, const GaloisKey& gk) {
+    return bfv_swap_rows(std::vector<BfvCiphertext>{ct}, gk)[0];
+}
+
+// batch_encode + encrypt_sk / encrypt_pk, and decrypt + batch_decode, composed on the device
+inline std::vector<BfvCiphertext> batch_encrypt(const std::vector<SlotVector>& values, const SecretKey* sk,
+                                                const PublicKey* pk, const BfvParamsPtr& prm, ChaChaRng& rng) {
+    const size_t Ln = prm->num_limbs() * prm->ring_degree;
+    auto flat = detail::flatten_slots(values, prm->ring_degree);
+    std::vector<uint64_t> ct(values.size() * 2 * Ln);
+    if (sk) {
+        detail::check(exacto_batch_encrypt_sk(prm->ctx(), flat.data(), sk->poly.data.data(), prm->sigma, rng.key,
+                                              rng.next(), ct.data(), values.size()));
+    } else {
+        std::vector<uint64_t> pkf(pk->pk0.data);
+        pkf.insert(pkf.end(), pk->pk1.data.begin(), pk->pk1.data.end());
+        detail::check(exacto_batch_encrypt_pk(prm->ctx(), flat.data(), pkf.data(), prm->sigma, rng.key, rng.next(),
+                                              ct.data(), values.size()));
+    }
+    return detail::unflatten(ct, values.size(), 2, prm);
+}
+inline BfvCiphertext batch_encrypt_sk(const SlotVector& values, const SecretKey& sk, const BfvParamsPtr& prm,
+                                      ChaChaRng& rng) {
+    return batch_encrypt({values}, &sk, nullptr, prm, rng)[0];
+}
+inline BfvCiphertext batch_encrypt_pk(const SlotVector& values, const PublicKey& pk, const BfvParamsPtr& prm,
+                                      ChaChaRng& rng) {
+    return batch_encrypt({values}, nullptr, &pk, prm, rng)[0];
+}
+inline std::vector<SlotVector> batch_decrypt(const std::vector<BfvCiphertext>& cts, const SecretKey& sk) {
+    if (cts.empty()) return {};
+    const BfvParams& prm = *cts[0].params;
+    const size_t polys = cts[0].c.size(), n = prm.ring_degree;
+    auto flat = detail::flatten(cts, polys);
+    std::vector<uint64_t> out(cts.size() * n);
+    detail::check(exacto_batch_decrypt(prm.ctx(), flat.data(), polys, sk.poly.data.data(), out.data(), cts.size()));
+    return detail::split_slots(out, cts.size(), n);
+}
+inline SlotVector batch_decrypt(const BfvCiphertext& ct, const SecretKey& sk) {
+    return batch_decrypt(std::vector<BfvCiphertext>{ct}, sk)[0];
+}
+
 // ---- plaintext operations and the trace (src/bfv/eval.rs:468-652)
 namespace detail {
 inline std::vector<uint64_t> flatten_pts(const std::vector<CoeffPoly>& pts, size_t n) {

@@ -534,6 +534,72 @@ int exacto_bfv_apply_automorphism(exacto_ctx* ctx, const uint64_t* ct, size_t po
 int exacto_bfv_apply_automorphism_dev(exacto_ctx* ctx, const uint64_t* ct, size_t polys, uint64_t element,
                                       const uint64_t* gk, size_t num_keys, uint64_t* out, size_t batch);
 
+/* ---- SIMD batching: slot encoding mod t, row rotations (replaces bfv/encoding.rs) ----
+ * The reference's encode_simd is coefficient packing ("not true SIMD", encoding.rs:30-31); this is the
+ * CRT batching it names.  It needs a prime plaintext modulus t == 1 (mod 2n) with 16 <= n <= 16384 and
+ * t < 2^32.  zeta = x^((t-1)/2n) for the smallest x >= 2 for which it has order 2n (the library's root
+ * rule applied to t).  A slot vector values[n] is a 2 x n/2 matrix, row 0 = values[0 .. n/2), row 1 =
+ * values[n/2 .. n).  With e_i = 3^i mod 2n, the plaintext m(X) mod t that encodes `values` satisfies
+ *     m(zeta^e_i) = values[i],   m(zeta^(2n - e_i)) = values[n/2 + i]     (0 <= i < n/2).
+ * So: the negacyclic product of plaintexts is the slot-wise product; sigma_{3^k} rotates both rows left
+ * by k; sigma_{2n-1} swaps the rows; the trace over exacto_required_trace_elements(n) leaves the sum
+ * of all slots in every slot.
+ * pt = [B][n] is exactly what exacto_encrypt_sk / exacto_bfv_plain_mul / exacto_bfv_plain_add take and
+ * what exacto_bfv_decrypt returns.  The transforms are one 32-bit kernel per direction (batch.hip).
+ * Errors come from a context's first batching call, never from exacto_ctx_create, and the same error
+ * is returned by every later batching call; every other entry point of such a context works as before:
+ *   InvalidParam    "batching requires a prime plaintext modulus t ≡ 1 (mod 2n), got t={t}, n={n}"
+ *   NotImplemented  "batching for plaintext moduli >= 2^32"   (a valid t >= 2^32)
+ * The tables (twiddles mod t, n^-1, the slot permutation) are built on the host and uploaded at that
+ * first call, which waits for the context's stream once; later calls do not.
+ *
+ * exacto_batch_info: 0 when the context batches (building the tables if need be), else the error;
+ *   *root (may be NULL) receives zeta.
+ * exacto_batch_encode: values [B][n] -> pt [B][n].  The host form rejects the first value >= t as
+ *   encode_simd does (encoding.rs:40-46): InvalidParam "plaintext {v} >= plain_modulus {t}".  The _dev
+ *   form cannot look at the values without waiting: it REDUCES every value mod t in the kernel.
+ * exacto_batch_decode: pt [B][n] -> values [B][n]; coefficients are reduced mod t in both forms.
+ * Both: out == in (in place) is allowed, any other overlap is InvalidParam; _dev buffers must be 16-byte
+ * aligned (InvalidParam); batch == 0 returns 0. */
+int exacto_batch_info(exacto_ctx* ctx, uint64_t* root);
+int exacto_batch_encode(exacto_ctx* ctx, const uint64_t* values, uint64_t* pt, size_t batch);
+int exacto_batch_encode_dev(exacto_ctx* ctx, const uint64_t* values, uint64_t* pt, size_t batch);
+int exacto_batch_decode(exacto_ctx* ctx, const uint64_t* pt, uint64_t* values, size_t batch);
+int exacto_batch_decode_dev(exacto_ctx* ctx, const uint64_t* pt, uint64_t* values, size_t batch);
+/* Galois elements of the slot matrix, host only, no context: 3^(steps mod n/2) mod 2n (negative steps
+ * rotate right) and 2n - 1.  n must be a power of two >= 4 (InvalidRingDegree). */
+int exacto_galois_element_rotate_rows(size_t n, int64_t steps, uint64_t* element);
+int exacto_galois_element_swap_rows(size_t n, uint64_t* element);
+/* Row rotation / row swap of ciphertexts: bit for bit exacto_bfv_apply_automorphism with the element
+ * above and gk that element's key, with the same errors.  steps == 0 (mod n/2) copies ct (out == ct
+ * allowed) and needs no key: gk may be NULL.  Well defined, and working, on a context that cannot
+ * batch (the automorphism does not depend on t). */
+int exacto_bfv_rotate_rows(exacto_ctx* ctx, const uint64_t* ct, size_t polys, int64_t steps, const uint64_t* gk,
+                           size_t num_keys, uint64_t* out, size_t batch);
+int exacto_bfv_rotate_rows_dev(exacto_ctx* ctx, const uint64_t* ct, size_t polys, int64_t steps, const uint64_t* gk,
+                               size_t num_keys, uint64_t* out, size_t batch);
+int exacto_bfv_swap_rows(exacto_ctx* ctx, const uint64_t* ct, size_t polys, const uint64_t* gk, size_t num_keys,
+                         uint64_t* out, size_t batch);
+int exacto_bfv_swap_rows_dev(exacto_ctx* ctx, const uint64_t* ct, size_t polys, const uint64_t* gk, size_t num_keys,
+                             uint64_t* out, size_t batch);
+/* Compositions on the context's stream, no host round trip: bit for bit exacto_batch_encode followed by
+ * exacto_encrypt_sk / exacto_encrypt_pk on the whole batch (values [B][n] instead of pt, the other
+ * arguments theirs), and exacto_bfv_decrypt followed by exacto_batch_decode (values_out [B][n]).  The
+ * plaintexts live in a context-owned buffer of one chunk (exacto_ctx_set_chunk).  Value range as in
+ * exacto_batch_encode: the host forms reject, the _dev forms reduce. */
+int exacto_batch_encrypt_sk(exacto_ctx* ctx, const uint64_t* values, const uint64_t* sk, double sigma,
+                            const uint64_t* key, uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_batch_encrypt_sk_dev(exacto_ctx* ctx, const uint64_t* values, const uint64_t* sk, double sigma,
+                                const uint64_t* key, uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_batch_encrypt_pk(exacto_ctx* ctx, const uint64_t* values, const uint64_t* pk, double sigma,
+                            const uint64_t* key, uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_batch_encrypt_pk_dev(exacto_ctx* ctx, const uint64_t* values, const uint64_t* pk, double sigma,
+                                const uint64_t* key, uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_batch_decrypt(exacto_ctx* ctx, const uint64_t* ct, size_t polys, const uint64_t* sk, uint64_t* values_out,
+                         size_t batch);
+int exacto_batch_decrypt_dev(exacto_ctx* ctx, const uint64_t* ct, size_t polys, const uint64_t* sk,
+                             uint64_t* values_out, size_t batch);
+
 /* Plaintext-ciphertext operations (CoeffsToSlots' linear layer), all in the NTT domain.
  * ct/out [B][polys][L][n]; pt [B][n] plaintext coefficients (any u64, reduced mod each q_i).
  *   bfv_plain_mul     replaces bfv::eval::bfv_plain_mul      (src/bfv/eval.rs:468-486)
