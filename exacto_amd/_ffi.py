@@ -189,6 +189,15 @@ _SIGS = [
     ("exacto_broadcast_galois_key", [_P, _P, C.c_int, _P, _SZ], C.c_int),
     ("exacto_rccl_allgather_u64", [_P, _P, _P, _P, _SZ], C.c_int),
     ("exacto_rccl_sync", [_P, _P], C.c_int),
+    ("exacto_galois_ntt_permutation", [_SZ, _U64, _P], C.c_int),
+    ("exacto_galois_keyset_create", [_P, _P, _SZ, _P, _SZ, C.POINTER(_P)], C.c_int),
+    ("exacto_galois_keyset_create_dev", [_P, _P, _SZ, _P, _SZ, C.POINTER(_P)], C.c_int),
+    ("exacto_galois_keyset_destroy", [_P], None),
+    ("exacto_galois_keyset_info", [_P, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(C.c_int)], C.c_int),
+    ("exacto_bfv_rotate_hoisted", [_P, _P, _P, _P, _SZ], C.c_int),
+    ("exacto_bfv_rotate_hoisted_dev", [_P, _P, _P, _P, _SZ], C.c_int),
+    ("exacto_bfv_linear_transform", [_P, _P, _P, _P, _P, _SZ], C.c_int),
+    ("exacto_bfv_linear_transform_dev", [_P, _P, _P, _P, _P, _SZ], C.c_int),
     ("exacto_last_error", [C.c_char_p, _SZ], _SZ),
     ("exacto_prof_enable", [_P, C.c_int], C.c_int),
     ("exacto_prof_read", [_P, C.c_int, C.POINTER(_U64), C.POINTER(C.c_double),
@@ -325,6 +334,53 @@ def galois_element_swap_rows(n: int) -> int:
     el = C.c_uint64(0)
     check(load().exacto_galois_element_swap_rows(n, C.byref(el)))
     return int(el.value)
+
+
+def galois_ntt_permutation(n: int, element: int) -> np.ndarray:
+    """perm [n] (uint32) with NTT(sigma_element(a))[p] = NTT(a)[perm[p]] in the library's NTT-domain order, the
+    same for every prime; element odd (taken mod 2n); host-only entry point."""
+    perm = np.zeros(max(int(n), 1), dtype=np.uint32)
+    check(load().exacto_galois_ntt_permutation(n, int(element) % (1 << 64), perm.ctypes.data))
+    return perm[:n]
+
+
+class GaloisKeySet:
+    """Galois keys prepared once for hoisted rotations (exacto_galois_keyset_create): the permutation tables
+    and the keys in the form the context's key switch consumes.  Holds a reference to its HipContext, so the
+    context outlives it; close() (or garbage collection) releases the device memory."""
+
+    def __init__(self, ctx: "HipContext", elements, gks, num_keys: int | None = None, dev: bool = False):
+        self.ctx = ctx
+        self.elements = [int(e) for e in elements]
+        els = _u64(self.elements) if self.elements else None
+        if dev:
+            gp, nk = ctx._p(gks), int(num_keys or 0)
+        else:
+            g = None if gks is None else _u64(gks)
+            nk = 0 if g is None or g.ndim != 5 else g.shape[1]
+            gp = g.ctypes.data if g is not None and g.size else None
+        h = C.c_void_p()
+        fn = ctx._lib.exacto_galois_keyset_create_dev if dev else ctx._lib.exacto_galois_keyset_create
+        check(fn(ctx._h, els.ctypes.data if els is not None else None, len(self.elements), gp, nk, C.byref(h)))
+        self._h = h
+        r, used, s = C.c_size_t(), C.c_size_t(), C.c_int()
+        check(ctx._lib.exacto_galois_keyset_info(h, C.byref(r), C.byref(used), C.byref(s)))
+        self.R, self.num_keys_used, self.ks32_primes = int(r.value), int(used.value), int(s.value)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            self.ctx._lib.exacto_galois_keyset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def dbfv_change_base_matrix(d: int, base: int, plain: int, new_base: int, new_d: int) -> np.ndarray:
@@ -844,6 +900,60 @@ class HipContext:
                                              gk.shape[0], out.ctypes.data, ct.shape[0]))
         return out
 
+    # ---- hoisted rotations and slot linear transforms (exacto_galois_keyset_*, exacto_hip.h)
+    def galois_keyset(self, elements, gks) -> "GaloisKeySet":
+        """elements [R], gks [R][num_keys][2][L][n] (host) -> a prepared key set; element 1 needs no key."""
+        return GaloisKeySet(self, elements, gks)
+
+    def galois_keyset_dev(self, elements, gks, num_keys) -> "GaloisKeySet":
+        """The same from device memory gks [R][num_keys][2][L][n] (may be released afterwards)."""
+        return GaloisKeySet(self, elements, gks, num_keys, dev=True)
+
+    def bfv_rotate_hoisted(self, ct, keyset: "GaloisKeySet") -> np.ndarray:
+        """ct [B][2][L][n] -> [B][R][2][L][n]: every automorphism of the set on the shared digits of c1 (the
+        same plaintexts as bfv_apply_automorphism, not its bits)."""
+        ct = _u64(ct)
+        out = np.zeros((ct.shape[0], keyset.R, 2, self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_bfv_rotate_hoisted(self._h, keyset.handle, ct.ctypes.data if ct.size else None,
+                                                  out.ctypes.data if out.size else None, ct.shape[0]))
+        return out
+
+    def bfv_linear_transform(self, ct, keyset: "GaloisKeySet", pts) -> np.ndarray:
+        """ct [B][2][L][n], pts [R][n] plaintext coefficients -> sum_r pts[r] * rotation r, [B][2][L][n]."""
+        ct, pts = _u64(ct), _u64(pts)
+        if pts.shape != (keyset.R, self.n):
+            raise ValueError(f"pts must be a [{keyset.R}][{self.n}] array")
+        out = np.zeros((ct.shape[0], 2, self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_bfv_linear_transform(self._h, keyset.handle, ct.ctypes.data if ct.size else None,
+                                                    pts.ctypes.data, out.ctypes.data if out.size else None,
+                                                    ct.shape[0]))
+        return out
+
+    def bfv_rotate_hoisted_dev(self, ct, keyset: "GaloisKeySet", out, batch):
+        check(self._lib.exacto_bfv_rotate_hoisted_dev(self._h, keyset.handle, self._p(ct), self._p(out), batch))
+
+    def bfv_linear_transform_dev(self, ct, keyset: "GaloisKeySet", pts, out, batch):
+        check(self._lib.exacto_bfv_linear_transform_dev(self._h, keyset.handle, self._p(ct), self._p(pts),
+                                                        self._p(out), batch))
+
+    def rotate_rows_keyset(self, steps, gks) -> "GaloisKeySet":
+        """A key set for row rotations by `steps` (gks[r] the key of 3^steps[r] mod 2n; ignored for steps == 0
+        mod n/2), for rotate_rows_many / batch_linear_transform."""
+        return self.galois_keyset([galois_element_rotate_rows(self.n, int(s)) for s in steps], gks)
+
+    def rotate_rows_many(self, ct, steps, keyset: "GaloisKeySet") -> np.ndarray:
+        """Both slot rows left by every steps[r] at once: ct [B][2][L][n] -> [B][R][2][L][n]; keyset holds the
+        elements 3^steps[r] mod 2n in this order (rotate_rows_keyset)."""
+        want = [galois_element_rotate_rows(self.n, int(s)) for s in steps]
+        if [e % (2 * self.n) for e in keyset.elements] != want:
+            raise ValueError("keyset does not hold the elements of these steps in this order")
+        return self.bfv_rotate_hoisted(ct, keyset)
+
+    def batch_linear_transform(self, ct, keyset: "GaloisKeySet", slot_diagonals) -> np.ndarray:
+        """sum_r w_r (.) rot_r(x) on slots: slot_diagonals [R][n] (values below t) are batch_encoded and
+        multiplied into the set's rotations of ct [B][2][L][n]."""
+        return self.bfv_linear_transform(ct, keyset, self.batch_encode(slot_diagonals))
+
     def batch_encrypt_sk(self, values, sk, key, stream=0, sigma=3.2) -> np.ndarray:
         """batch_encode then encrypt_sk on the device: values [B][n] -> ct [B][2][L][n]."""
         k, v, sk = self._key(key), self._batch_rows(values, "values"), _u64(sk)
@@ -1063,6 +1173,10 @@ class HipContext:
 
     def bfv_add_dev(self, a, polys1, b, polys2, out, batch):
         check(self._lib.exacto_bfv_add_dev(self._h, self._p(a), polys1, self._p(b), polys2, self._p(out), batch))
+
+    def bfv_plain_mul_dev(self, ct, polys, pt, out, batch):
+        """ct [batch][polys][L][n] times pt [batch][n] plaintext coefficients, item by item."""
+        check(self._lib.exacto_bfv_plain_mul_dev(self._h, self._p(ct), polys, self._p(pt), self._p(out), batch))
 
     def bfv_sub_dev(self, a, polys1, b, polys2, out, batch):
         check(self._lib.exacto_bfv_sub_dev(self._h, self._p(a), polys1, self._p(b), polys2, self._p(out), batch))

@@ -4675,6 +4675,300 @@ extern "C" int exacto_bfv_swap_rows(exacto_ctx* c, const uint64_t* ct, size_t po
     return exacto_bfv_apply_automorphism(c, ct, polys, 2 * (u64)c->n - 1, gk, num_keys, out, B);
 }
 
+// ---- hoisted rotations and slot linear transforms on a prepared Galois key set (hoist.hip)
+
+// perm[p] = the storage position whose value lands at storage position p under sigma_element:
+// NTT(sigma(a))[p] = NTT(a)[perm[p]].  Storage position p holds evaluation j = (p mod n/16) 16 + p / (n/16)
+// (evaluation j at (j mod 16) n/16 + j / 16), evaluation j is the value at psi^(2 brv(j) + 1), and
+// sigma_k(a)(x) = a(x^k): evaluation j of sigma_k(a) is evaluation j' of a with
+// 2 brv(j') + 1 = (2 brv(j) + 1) k mod 2n.  The same table for every prime.  Host only.
+extern "C" int exacto_galois_ntt_permutation(size_t n, uint64_t element, uint32_t* perm) {
+    if (!perm) return invalid_param("null argument");
+    if (n < 16 || n > 16384 || (n & (n - 1)) != 0)
+        return fail(EXACTO_ERR_INVALID_RING_DEGREE,
+                    "ring degree must be a power of 2 in 16..16384, got " + std::to_string(n));
+    const u64 k = element % (2 * (u64)n);
+    if ((k & 1) == 0) return invalid_param("hoisted automorphisms require odd Galois elements");
+    int logn = 0;
+    while (((size_t)1 << logn) < n) ++logn;
+    const size_t m = n / 16;
+    for (size_t p = 0; p < n; ++p) {
+        const int j = (int)((p % m) * 16 + p / m);
+        const u64 e = ((2 * (u64)bitrev(j, logn) + 1) * k) % (2 * (u64)n);
+        const size_t j2 = (size_t)bitrev((int)((e - 1) / 2), logn);
+        perm[p] = (uint32_t)((j2 % 16) * m + j2 / 16);
+    }
+    return 0;
+}
+
+struct exacto_galois_keyset {
+    int device = 0, n = 0, L = 0;
+    std::vector<u64> primes;      // the ciphertext primes of the context it was prepared on
+    u64 gbase = 0;
+    size_t R = 0;
+    int guse = 0;                 // min(G, num_keys); 0: every element is the identity
+    bool k32 = false;             // keys as ks32_convert_key's rows in the narrow 31-bit basis
+    int S = 0, mac_form = 0;
+    uint32_t* d_perm = nullptr;   // [R][n]
+    unsigned char* d_ident = nullptr;  // [R]
+    u64 *d_keys = nullptr, *d_keys_s = nullptr;   // limb-wise: [R][guse][2][L][n] and Shoup companions
+    uint32_t* d_rs = nullptr;     // 31-bit path: [R][guse][2L][S][n]
+};
+
+extern "C" void exacto_galois_keyset_destroy(exacto_galois_keyset* ks) {
+    if (!ks) return;
+    (void)hipSetDevice(ks->device);
+    free_dev(ks->d_perm); free_dev(ks->d_ident); free_dev(ks->d_keys); free_dev(ks->d_keys_s); free_dev(ks->d_rs);
+    delete ks;
+}
+
+extern "C" int exacto_galois_keyset_info(const exacto_galois_keyset* ks, size_t* R, size_t* num_keys_used,
+                                         int* ks32_primes) {
+    if (!ks) return invalid_param("null key set");
+    if (R) *R = ks->R;
+    if (num_keys_used) *num_keys_used = (size_t)ks->guse;
+    if (ks32_primes) *ks32_primes = ks->k32 ? ks->S : 0;
+    return 0;
+}
+
+// the single automorphism's choice of key switch (exacto_bfv_apply_automorphism_dev)
+static bool hoist_k32(const exacto_ctx* c) {
+    const bool d16 = c->digit16 && c->gbase <= 65536;
+    return d16 && c->ks32 && c->kn.S > 0 && c->path == EXACTO_PATH_EXACT_RNS;
+}
+
+extern "C" int exacto_galois_keyset_create_dev(exacto_ctx* c, const uint64_t* elements, size_t R, const uint64_t* gks,
+                                               size_t num_keys, exacto_galois_keyset** out) {
+    if (int e = check_ctx(c)) return e;
+    if (!out || !elements) return invalid_param("null argument");
+    *out = nullptr;
+    if (R == 0) return invalid_param("galois key set needs at least one element");
+    if (R > 65535) return invalid_param("galois key set holds at most 65535 elements");
+    const int n = c->n, L = c->L;
+    const long Ln = (long)L * n;
+    std::vector<unsigned char> ident(R);
+    std::vector<uint32_t> perm(R * (size_t)n);
+    bool keyed = false;
+    for (size_t r = 0; r < R; ++r) {
+        if (int e = exacto_galois_ntt_permutation((size_t)n, elements[r], perm.data() + r * n)) return e;
+        ident[r] = elements[r] % (2 * (u64)n) == 1;
+        keyed |= !ident[r];
+    }
+    if (keyed && num_keys == 0) return invalid_param("galois key is empty");
+    if (keyed && !gks) return invalid_param("null argument");
+    std::unique_ptr<exacto_galois_keyset, void (*)(exacto_galois_keyset*)> ks(new exacto_galois_keyset,
+                                                                             exacto_galois_keyset_destroy);
+    ks->device = c->device; ks->n = n; ks->L = L;
+    ks->primes.assign(c->primes.begin(), c->primes.begin() + L);
+    ks->gbase = c->gbase;
+    ks->R = R;
+    ks->guse = keyed ? (int)std::min<size_t>(c->G, num_keys) : 0;
+    ks->k32 = keyed && hoist_k32(c);
+    HIP_TRY(dev_alloc((void**)&ks->d_perm, perm.size() * sizeof(uint32_t)));
+    HIP_TRY(dev_alloc((void**)&ks->d_ident, (R + 7) / 8 * 8));
+    if (int e = upload(c, ks->d_perm, perm.data(), perm.size() * sizeof(uint32_t))) return e;
+    if (int e = upload(c, ks->d_ident, ident.data(), R)) return e;
+    const size_t guse = (size_t)ks->guse;
+    if (ks->k32) {
+        const Ks32Basis& kb = c->kn;   // the narrow basis: its bound holds for any key (as the single call)
+        ks->S = kb.S; ks->mac_form = kb.mac_form;
+        const long rows = (long)guse * 2 * L;
+        HIP_TRY(dev_alloc((void**)&ks->d_rs, R * (size_t)rows * kb.S * n * sizeof(uint32_t)));
+        Scratch kc;
+        HIP_TRY(kc.alloc((size_t)rows * n * sizeof(u64), c->stream, c->pool, c->debug_scratch));
+        for (size_t r = 0; r < R; ++r) {
+            if (ident[r]) continue;   // its slot is never read
+            NttBatch nb{};
+            nb.src = gks + r * num_keys * 2 * Ln; nb.src_item_stride = 2 * Ln;
+            nb.dst = kc.as<u64>(); nb.dst_item_stride = 2 * Ln;
+            nb.ppi = 2 * L; nb.prime_base = 0; nb.period = L;
+            if (int e = run_ntt(c, nb, rows, true)) return e;
+            ks32_key(kc.as<u64>(), ks->d_rs + r * (size_t)rows * kb.S * n, rows, L, kb.S, c->logn, kb.d_p32, c->d_primes,
+                     kb.mac_form, c->stream);
+            CHECK_LAUNCH();
+        }
+    } else if (keyed) {
+        const size_t per = guse * 2 * (size_t)Ln;
+        HIP_TRY(dev_alloc((void**)&ks->d_keys, R * per * sizeof(u64)));
+        HIP_TRY(dev_alloc((void**)&ks->d_keys_s, R * per * sizeof(u64)));
+        for (size_t r = 0; r < R; ++r) {
+            if (ident[r])
+                launch_rows(ks->d_keys + r * per, 0, nullptr, 0, (long)per, 1, c->stream);
+            else
+                HIP_TRY(dev_copy(ks->d_keys + r * per, gks + r * num_keys * 2 * Ln, per * sizeof(u64), c->stream));
+            CHECK_LAUNCH();
+        }
+        launch_shoup_companions(ks->d_keys, ks->d_keys_s, (long)(R * per), n, L, c->d_primes, c->stream);
+        CHECK_LAUNCH();
+    }
+    // the caller's gks may go once this returns
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out = ks.release();
+    return 0;
+}
+
+extern "C" int exacto_galois_keyset_create(exacto_ctx* c, const uint64_t* elements, size_t R, const uint64_t* gks,
+                                           size_t num_keys, exacto_galois_keyset** out) {
+    if (int e = check_ctx(c)) return e;
+    if (!gks || num_keys == 0 || R == 0 || !elements || !out)   // nothing to stage: the device form's checks
+        return exacto_galois_keyset_create_dev(c, elements, R, nullptr, num_keys, out);
+    const size_t bytes = R * num_keys * 2 * c->L * poly_bytes(c);
+    u64* d = nullptr;
+    HIP_TRY(dev_alloc((void**)&d, bytes));
+    int rc = upload(c, d, gks, bytes);
+    if (rc == 0) rc = exacto_galois_keyset_create_dev(c, elements, R, d, num_keys, out);
+    free_dev(d);
+    return rc;
+}
+
+static int hoist_check(exacto_ctx* c, const exacto_galois_keyset* ks) {
+    if (!ks) return invalid_param("null key set");
+    if (ks->n != c->n || ks->L != c->L || ks->gbase != c->gbase || ks->device != c->device ||
+        !std::equal(ks->primes.begin(), ks->primes.end(), c->primes.begin()))
+        return invalid_param("galois key set was prepared on a context with other parameters");
+    if (ks->guse > 0 && (ks->k32 != hoist_k32(c) || (ks->k32 && (ks->S != c->kn.S || ks->mac_form != c->kn.mac_form))))
+        return invalid_param("galois key set was prepared for another key-switch path");
+    return 0;
+}
+
+// out[b][r] = (sigma_r(c0) + sum_g sigma_r(d_g) k_{r,g,0}, sum_g sigma_r(d_g) k_{r,g,1}), d_g the digits of c1
+// itself; pts != nullptr: out[b] = sum_r pt_r out[b][r] instead (pts [R][n] plaintext coefficients).
+static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* ct, const u64* pts, bool lt, u64* out,
+                      size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = hoist_check(c, ks)) return e;
+    if (B == 0) return 0;
+    if (!ct || !out || (lt && !pts)) return invalid_param("null argument");
+    const int n = c->n, L = c->L, R = (int)ks->R, guse = ks->guse;
+    const long Ln = (long)L * n;
+    const size_t in_words = B * 2 * (size_t)Ln, out_words = in_words * (lt ? 1 : ks->R);
+    if (out < ct + in_words && ct < out + out_words) return invalid_param("out must not overlap ct");
+    const bool d16 = c->digit16 && c->gbase <= 65536;
+    const bool k32 = ks->k32;
+    const Ks32Basis& kb = c->kn;
+    if (lt)
+        if (int e = lift_plain(c, pts, R, false)) return e;   // pl_buf [R][L][n], made before the fork
+    // chunk: the 31-bit path's sums (S / 2 outputs per rotation) and, for the linear transform, its
+    // rotations stay within R outputs per chunk item of c->chunk; one launch's blocks within 2^30
+    size_t C = std::min<size_t>(c->chunk, B);
+    if (k32) C = std::max<size_t>(1, C * 2 / (size_t)(kb.S + (lt ? 2 : 0)));
+    const size_t nblk = (size_t)((Ln + 255) / 256);
+    C = std::max<size_t>(1, std::min<size_t>(C, ((size_t)1 << 30) / (nblk * ks->R)));
+    if (int e = ensure_workspace(c, C)) return e;
+    const long nchunks = (long)((B + C - 1) / C);
+    const int nl_max = (c->dual && !c->prof) ? (int)std::min<long>(c->lanes, nchunks) : 1;
+    // per-lane scratch, allocated before the fork and released after the join (declared before LaneJoin)
+    const size_t u_words = k32 ? C * ks->R * 2 * L * (size_t)kb.S * n : 0;            // uint32
+    const size_t h_words = (k32 && lt) ? C * ks->R * 2 * (size_t)Ln : 0;              // u64
+    Scratch us, hs;
+    if (u_words) HIP_TRY(us.alloc(u_words * nl_max * sizeof(uint32_t), c->stream, c->pool, c->debug_scratch));
+    if (h_words) HIP_TRY(hs.alloc(h_words * nl_max * sizeof(u64), c->stream, c->pool, c->debug_scratch));
+    int nl = 1;
+    if (int e = fork_lanes(c, nchunks, C, &nl)) return e;
+    LaneJoin join{c, nl};
+    for (size_t s0 = 0; s0 < B; s0 += C) {
+        const int cnt = (int)std::min(C, B - s0);
+        const int li = (int)((s0 / C) % (size_t)nl);
+        LaneGuard lane(c, li);
+        const u64* src = ct + s0 * 2 * Ln;
+        u64* dst = out + s0 * 2 * Ln * (lt ? 1 : ks->R);
+        if (guse > 0) {
+            // c1 alone back to coefficients, its exact CRT and gadget digits, one digit transform
+            NttBatch nb{};
+            nb.src = src + Ln; nb.src_item_stride = 2 * Ln;
+            nb.dst = c->ws_coefQ; nb.dst_item_stride = Ln;
+            nb.ppi = L; nb.prime_base = 0; nb.period = L;
+            if (int e = run_ntt(c, nb, (long)cnt * L, true)) return e;
+            launch_decompose(c->ws_coefQ, Ln, c->ws_D, guse, cnt, n, c->d_crt, c->d_primes, L, c->stream,
+                             d16 ? c->ws_D16 : nullptr);
+            CHECK_LAUNCH();
+        }
+        if (k32) {
+            uint32_t* U = us.as<uint32_t>() + (size_t)li * u_words;
+            u64* H = lt ? hs.as<u64>() + (size_t)li * h_words : dst;
+            {
+                ProfScope pd(c, PK_KS_DIGITS, (u64)cnt * guse * kb.S, (2.0 + 4.0 * kb.S) * n * (double)cnt * guse);
+                ks32_digits(c->ws_D16, c->ws_DS, cnt, guse, kb.S, c->logn, kb.d_p32, kb.mac_form, c->stream);
+            }
+            // The basis bound of setup_ks32 covers sigma(d) unchanged: sigma permutes a digit's coefficients
+            // up to sign, so the digit magnitudes, and with them |sum_g sigma(d_g) * r_g|, are the same.
+            {
+                ProfScope pm(c, PK_KS_MAC, (u64)cnt * R * 2 * L * kb.S,
+                             4.0 * n * kb.S * ((double)cnt * R * (guse + 2 * L) + (double)R * guse * 2 * L));
+                ks32_mac_hoist(c->ws_DS, ks->d_rs, U, ks->d_perm, ks->d_ident, cnt, R, guse, L, kb.S, n, kb.d_p32,
+                               kb.mac_form, c->stream);
+            }
+            CHECK_LAUNCH();
+            // the lift adds into a zeroed coefficient buffer; both components forward; c0 o perm_r joins
+            // in the NTT domain
+            launch_rows(H, 0, nullptr, 0, (long)cnt * R * 2 * Ln, 1, c->stream);
+            {
+                ProfScope pc(c, PK_KS_CRT, (u64)cnt * R * 2 * L, (4.0 * kb.S + 16.0) * n * (double)cnt * R * 2 * L);
+                ks32_crt(U, H, 2 * Ln, cnt * R, L, kb.S, c->logn, kb.d_kst, kb.d_p32, c->d_primes, kb.mac_form,
+                         c->stream, c->ks_fpc && kb.fpc_max >= 1);
+            }
+            CHECK_LAUNCH();
+            NttBatch rb{};
+            rb.src = H; rb.src_item_stride = 2 * Ln;
+            rb.dst = H; rb.dst_item_stride = 2 * Ln;
+            rb.ppi = 2 * L; rb.prime_base = 0; rb.period = L;
+            if (int e = run_ntt(c, rb, (long)cnt * R * 2 * L, false)) return e;
+            launch_hoist_c0(src, ks->d_perm, ks->d_ident, H, R, cnt, n, L, c->d_primes, c->stream);
+            if (lt) launch_hoist_ptsum(H, c->pl_buf, dst, R, cnt, n, L, c->d_primes, c->stream);
+            CHECK_LAUNCH();
+            continue;
+        }
+        if (guse > 0) {
+            NttBatch db = contiguous(c->ws_D, cnt, (long)guse * L, 0, L, n);
+            if (d16) {
+                db.src16 = c->ws_D16;
+                db.src16_item_stride = (long)guse * n;
+            }
+            if (int e = run_ntt(c, db, (long)cnt * guse * L, false)) return e;
+        }
+        {
+            ProfScope pm(c, PK_RELIN_MAC, (u64)cnt * R * 2 * L,
+                         8.0 * Ln * ((double)cnt * R * (guse + 1 + (lt ? 0 : 2)) + (double)R * guse * 4));
+            launch_hoist_mac(lt, src, c->ws_D, ks->d_keys, ks->d_keys_s, ks->d_perm, ks->d_ident,
+                             lt ? c->pl_buf : nullptr, dst, R, guse, cnt, n, L, c->d_primes, c->stream);
+        }
+        CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+extern "C" int exacto_bfv_rotate_hoisted_dev(exacto_ctx* c, const exacto_galois_keyset* ks, const uint64_t* ct,
+                                             uint64_t* out, size_t B) {
+    return hoist_core(c, ks, ct, nullptr, false, out, B);
+}
+
+extern "C" int exacto_bfv_linear_transform_dev(exacto_ctx* c, const exacto_galois_keyset* ks, const uint64_t* ct,
+                                               const uint64_t* pts, uint64_t* out, size_t B) {
+    return hoist_core(c, ks, ct, pts, true, out, B);
+}
+
+extern "C" int exacto_bfv_rotate_hoisted(exacto_ctx* c, const exacto_galois_keyset* ks, const uint64_t* ct,
+                                         uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = hoist_check(c, ks)) return e;
+    if (B == 0) return 0;
+    if (!ct || !out) return invalid_param("null argument");
+    const size_t ctb = B * 2 * c->L * poly_bytes(c);
+    return host_call(c, {{ct, ctb}}, ctb * ks->R, out,
+                     [&](std::vector<u64*>& d, u64* o) { return hoist_core(c, ks, d[0], nullptr, false, o, B); });
+}
+
+extern "C" int exacto_bfv_linear_transform(exacto_ctx* c, const exacto_galois_keyset* ks, const uint64_t* ct,
+                                           const uint64_t* pts, uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = hoist_check(c, ks)) return e;
+    if (B == 0) return 0;
+    if (!ct || !out || !pts) return invalid_param("null argument");
+    const size_t ctb = B * 2 * c->L * poly_bytes(c);
+    return host_call(c, {{ct, ctb}, {pts, ks->R * poly_bytes(c)}}, ctb, out,
+                     [&](std::vector<u64*>& d, u64* o) { return hoist_core(c, ks, d[0], d[1], true, o, B); });
+}
+
 // encode + encrypt chunk by chunk through batch_buf: the chunk's items keep the sample indices they
 // have in one exacto_encrypt_* call over the whole batch, so the ciphertexts are that call's bit for bit
 static int batch_encrypt_dev(exacto_ctx* c, const uint64_t* values, const uint64_t* sk, const uint64_t* pk,

@@ -146,6 +146,11 @@ void ks32_key_norms(const u64* K, u64* out, long rows, int L, int n, const Prime
 // U [items][2L][S][n] = sum_g DS (.) RS
 void ks32_mac(const uint32_t* DS, const uint32_t* RS, uint32_t* U, int items, int G, int L, int S, int n,
               const Prime32* primes, int mac_form, hipStream_t st);
+// hoisted rotations: U [items][R][2L][S][n] = sum_g (DS_g o perm_r) (.) RSK [r][g], perm [R][n] storage
+// positions, ident [R] non-zero for the identity element (no key read, zero sums); R <= 65535
+void ks32_mac_hoist(const uint32_t* DS, const uint32_t* RSK, uint32_t* U, const uint32_t* perm,
+                    const unsigned char* ident, int items, int R, int G, int L, int S, int n, const Prime32* primes,
+                    int mac_form, hipStream_t st);
 // R[item][c][l] += centred lift of INTT(U[item][c][l][.]) mod q_l (every q_l = 2^60 - d, d < 2^24)
 // fpc: the lift by a rounded float sum (ks32_dev.hpp ks32_fpc_one; taken when S <= 3 or the primes are
 // below 2^32 / 3, and the caller checked the basis' fpc_max)
@@ -273,6 +278,19 @@ void debug_watch_set(const void* lo, const void* hi, uint32_t* hit, hipStream_t 
 void launch_relin_mac(const u64* base, long base_stride, const u64* D, const u64* rlk, const u64* rlk_s,
                       int guse, u64* out, long out_stride, int items, int n, int L, const PrimeConst* primes,
                       hipStream_t s);
+
+// ---- hoisted rotations (hoist.hip): ct [items][2][L][n], D [items][guse][L][n] the transformed digits of c1,
+// keys / keys_s [R][guse][2][L][n] with Shoup companions, perm [R][n], ident [R]
+// lt: out [items][2][L][n] = sum_r pts[r] (.) rotation r (pts [R][L][n]); otherwise out [items][R][2][L][n]
+void launch_hoist_mac(bool lt, const u64* ct, const u64* D, const u64* keys, const u64* keys_s, const uint32_t* perm,
+                      const unsigned char* ident, const u64* pts, u64* out, int R, int guse, int items, int n, int L,
+                      const PrimeConst* primes, hipStream_t s);
+// H [items][R][2][L][n] += (c0 o perm_r, 0) (identity: += the input ciphertext)
+void launch_hoist_c0(const u64* ct, const uint32_t* perm, const unsigned char* ident, u64* H, int R, int items, int n,
+                     int L, const PrimeConst* primes, hipStream_t s);
+// out [items][2][L][n] = sum_r pts[r] (.) H[item][r]
+void launch_hoist_ptsum(const u64* H, const u64* pts, u64* out, int R, int items, int n, int L,
+                        const PrimeConst* primes, hipStream_t s);
 
 enum class PwOp : int { Add = 0, Sub = 1, Neg = 2, Mul = 3, ScalarMul = 4, Copy = 5 };
 void launch_pointwise(PwOp op, const u64* a, const u64* b, u64* out, long polys, int n, int L,

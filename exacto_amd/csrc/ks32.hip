@@ -203,6 +203,69 @@ ks32_mac_kernel(const int* __restrict__ DS, const int* __restrict__ RS, uint32_t
     }
 }
 
+// The hoisted form of ks32_mac_kernel (hoist.hip): rotation r = blockIdx.z of every item reads the digit
+// residues of the item's own c1 through perm_r (NTT(sigma_r(d_g)) = DS_g o perm_r, a 4-byte gather inside
+// one n-word row that the R rotations of an item share in L2) and key slice r of RSK [R][G][CL][S][n],
+// staged in LDS as above.  U [item][R][cl][s][n].  An identity rotation (ident[r]) reads no key and
+// writes zero sums.
+template <int CLB, int NW, int RUN, bool LZ = false>
+__global__ void __launch_bounds__(NW * 64)
+ks32_mac_hoist_kernel(const int* __restrict__ DS, const int* __restrict__ RSK, uint32_t* __restrict__ U,
+                      const uint32_t* __restrict__ perm, const unsigned char* __restrict__ ident, int G, int CL, int S,
+                      int items, int n, const Prime32* __restrict__ primes) {
+    extern __shared__ int kl[];                // [g][cl - cl0][lane]
+    constexpr int IG = 4 * NW;                 // items per block
+    const int lane = threadIdx.x & (KS_LS - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / KS_LS);
+    const int nb = n / KS_LS;
+    const int jb = blockIdx.x % nb;
+    const int s = (blockIdx.x / nb) % S;
+    const int cl0 = (blockIdx.x / (nb * S)) * CLB;
+    const int r = blockIdx.z, R = gridDim.z;
+    const int j = jb * KS_LS + lane;
+    const Prime32& P = primes[s];
+    const int it_end = min(items, (int)(blockIdx.y + 1) * IG);
+    if (ident[r]) {
+        for (int it = blockIdx.y * IG + wave; it < it_end; it += NW)
+#pragma unroll
+            for (int c = 0; c < CLB; ++c) U[((((long)it * R + r) * CL + cl0 + c) * S + s) * n + j] = 0;
+        return;
+    }
+    const int* RS = RSK + (long)r * G * CL * S * n;
+    for (int rr = wave; rr < G * CLB; rr += NW) {
+        const int g = rr / CLB, c = rr - g * CLB;
+        kl[rr * KS_LS + lane] = RS[(((long)g * CL + cl0 + c) * S + s) * n + jb * KS_LS + lane];
+    }
+    __syncthreads();
+    const int pj = (int)perm[(long)r * n + j];
+    for (int it = blockIdx.y * IG + wave; it < it_end; it += NW) {
+        const int* dp = DS + ((long)it * G * S + s) * n + pj;
+        long long acc[CLB];
+#pragma unroll
+        for (int c = 0; c < CLB; ++c) acc[c] = 0;
+        for (int g0 = 0; g0 < G; g0 += RUN) {
+            int d[RUN];
+#pragma unroll
+            for (int e = 0; e < RUN; ++e) d[e] = dp[(long)min(g0 + e, G - 1) * S * n];
+#pragma unroll
+            for (int e = 0; e < RUN; ++e) d[e] = g0 + e < G ? d[e] : 0;
+#pragma unroll
+            for (int e = 0; e < RUN; ++e) {
+                const int* kg = kl + (min(g0 + e, G - 1) * CLB) * KS_LS + lane;
+#pragma unroll
+                for (int c = 0; c < CLB; ++c) acc[c] += (long long)d[e] * kg[c * KS_LS];
+            }
+            if (g0 + RUN < G) {
+#pragma unroll
+                for (int c = 0; c < CLB; ++c) acc[c] = red_s64_lazy(acc[c], P);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CLB; ++c)
+            U[((((long)it * R + r) * CL + cl0 + c) * S + s) * n + j] = LZ ? red_s64_lz(acc[c], P) : red_s64(acc[c], P);
+    }
+}
+
 template <int LOGN, int S, bool LAZY, bool FPC>
 __global__ void __launch_bounds__((1 << LOGN) / 16)
 ks32_crt_kernel(const uint32_t* __restrict__ U, u64* __restrict__ R, long r_stride, int L,
@@ -377,6 +440,38 @@ void ks32_mac(const uint32_t* DS, const uint32_t* RS, uint32_t* U, int items, in
 // mac_form: 0 primes up to 2^31 (7 products per reduction), 1 below 2^32 / 3 (12), 2 below 2^30
 // (12, lazy output)
 #define MAC_(C_, W_, R_, Z_) EXACTO_LAUNCH((ks32_mac_kernel<C_, W_, R_, Z_>), grid, dim3(W_ * 64), lds, st, ds, rs, U, G, CL, S, items, n, primes)
+#define MAC(C_)                                                  \
+    do {                                                         \
+        if (mac_form == 2) { if (NW == 8) MAC_(C_, 8, 12, true); else MAC_(C_, 4, 12, true); } \
+        else if (mac_form == 1) { if (NW == 8) MAC_(C_, 8, 12, false); else MAC_(C_, 4, 12, false); } \
+        else { if (NW == 8) MAC_(C_, 8, 7, false); else MAC_(C_, 4, 7, false); }          \
+    } while (0)
+    switch (CLB) {
+        case 8: MAC(8); break;
+        case 6: MAC(6); break;
+        case 4: MAC(4); break;
+        case 3: MAC(3); break;
+        case 2: MAC(2); break;
+        default: MAC(1); break;
+    }
+#undef MAC
+#undef MAC_
+}
+
+void ks32_mac_hoist(const uint32_t* DS, const uint32_t* RSK, uint32_t* U, const uint32_t* perm,
+                    const unsigned char* ident, int items, int R, int G, int L, int S, int n, const Prime32* primes,
+                    int mac_form, hipStream_t st) {
+    if (items <= 0 || R <= 0) return;
+    const int CL = 2 * L;
+    // the block shape of ks32_mac, with the rotation in grid.z
+    int CLB = CL;
+    while (CLB > 1 && (CL % CLB != 0 || (size_t)G * CLB * KS_LS * sizeof(int) > 65536)) --CLB;
+    const size_t lds = (size_t)G * CLB * KS_LS * sizeof(int);
+    const int NW = lds > 32768 ? 8 : 4;
+    const dim3 grid((unsigned)((n / KS_LS) * S * (CL / CLB)), (unsigned)((items + 4 * NW - 1) / (4 * NW)), (unsigned)R);
+    const int* ds = reinterpret_cast<const int*>(DS);
+    const int* rs = reinterpret_cast<const int*>(RSK);
+#define MAC_(C_, W_, R_, Z_) EXACTO_LAUNCH((ks32_mac_hoist_kernel<C_, W_, R_, Z_>), grid, dim3(W_ * 64), lds, st, ds, rs, U, perm, ident, G, CL, S, items, n, primes)
 #define MAC(C_)                                                  \
     do {                                                         \
         if (mac_form == 2) { if (NW == 8) MAC_(C_, 8, 12, true); else MAC_(C_, 4, 12, true); } \

@@ -605,6 +605,97 @@ inline BfvCiphertext bfv_swap_rows(const BfvCiphertext& ct, const GaloisKey& gk)
     return bfv_swap_rows(std::vector<BfvCiphertext>{ct}, gk)[0];
 }
 
+// ---- hoisted rotations and slot linear transforms (exacto_hip.h, "Hoisted rotations ...")
+// perm[p]: NTT(sigma_element(a))[p] = NTT(a)[perm[p]] in the library's NTT-domain order; element odd
+inline std::vector<uint32_t> galois_ntt_permutation(size_t n, uint64_t element) {
+    std::vector<uint32_t> perm(n ? n : 1);
+    detail::check(exacto_galois_ntt_permutation(n, element, perm.data()));
+    perm.resize(n);
+    return perm;
+}
+
+// Galois keys prepared once for hoisted rotations.  keys[r] is the key of elements()[r]; an identity
+// element (1 mod 2n) takes no key: pass a default-constructed GaloisKey with that element.  The set keeps its
+// parameters (and with them the context) alive and releases its device memory first.
+class GaloisKeySet {
+public:
+    GaloisKeySet(const BfvParamsPtr& prm, const std::vector<GaloisKey>& keys) : params_(prm) {
+        const size_t Ln = prm->num_limbs() * prm->ring_degree;
+        size_t nk = 0;
+        for (const auto& k : keys) {
+            elements_.push_back(k.element);
+            nk = std::max(nk, k.keys.size());
+        }
+        std::vector<uint64_t> flat(keys.size() * nk * 2 * Ln, 0);
+        for (size_t r = 0; r < keys.size(); ++r) {
+            if (keys[r].keys.empty()) continue;   // identity: the slot is never read
+            if (keys[r].keys.size() != nk) throw ExactoError(EXACTO_ERR_INVALID_PARAM, "invalid parameter: galois keys of one set need the same number of digits");
+            const auto f = detail::flatten_key(keys[r].keys);
+            std::copy(f.begin(), f.end(), flat.begin() + r * nk * 2 * Ln);
+        }
+        detail::check(exacto_galois_keyset_create(prm->ctx(), elements_.data(), elements_.size(),
+                                                  flat.empty() ? nullptr : flat.data(), nk, &h_));
+    }
+    GaloisKeySet(const GaloisKeySet&) = delete;
+    GaloisKeySet& operator=(const GaloisKeySet&) = delete;
+    GaloisKeySet(GaloisKeySet&& o) noexcept : params_(std::move(o.params_)), elements_(std::move(o.elements_)), h_(o.h_) {
+        o.h_ = nullptr;
+    }
+    ~GaloisKeySet() { exacto_galois_keyset_destroy(h_); }
+    const exacto_galois_keyset* handle() const { return h_; }
+    const std::vector<uint64_t>& elements() const { return elements_; }
+    size_t size() const { return elements_.size(); }
+    const BfvParamsPtr& params() const { return params_; }
+    // the 31-bit primes of the set's key switch (0: the limb-wise multiply-accumulate)
+    int ks32_primes() const {
+        int s = 0;
+        detail::check(exacto_galois_keyset_info(h_, nullptr, nullptr, &s));
+        return s;
+    }
+
+private:
+    BfvParamsPtr params_;
+    std::vector<uint64_t> elements_;
+    exacto_galois_keyset* h_ = nullptr;
+};
+
+// out[b][r] = the set's automorphism r of cts[b] on the shared gadget digits of its c1: the same plaintexts
+// and noise bound as bfv_apply_automorphism, not its bits
+inline std::vector<std::vector<BfvCiphertext>> bfv_rotate_hoisted(const std::vector<BfvCiphertext>& cts,
+                                                                  const GaloisKeySet& ks) {
+    if (cts.empty()) return {};
+    const BfvParams& prm = *cts[0].params;
+    if (cts[0].c.size() != 2) throw ExactoError(EXACTO_ERR_INVALID_PARAM, "invalid parameter: automorphism requires degree-1 ciphertext");
+    auto flat = detail::flatten(cts, 2);
+    std::vector<uint64_t> out(flat.size() * ks.size());
+    detail::check(exacto_bfv_rotate_hoisted(prm.ctx(), ks.handle(), flat.data(), out.data(), cts.size()));
+    auto all = detail::unflatten(out, cts.size() * ks.size(), 2, cts[0].params);
+    std::vector<std::vector<BfvCiphertext>> res(cts.size());
+    for (size_t b = 0; b < cts.size(); ++b)
+        res[b].assign(all.begin() + b * ks.size(), all.begin() + (b + 1) * ks.size());
+    return res;
+}
+inline std::vector<BfvCiphertext> bfv_rotate_hoisted(const BfvCiphertext& ct, const GaloisKeySet& ks) {
+    return bfv_rotate_hoisted(std::vector<BfvCiphertext>{ct}, ks)[0];
+}
+
+// out[b] = sum_r pts[r] * (automorphism r of cts[b]); pts[r] plaintext coefficients, lifted as bfv_plain_mul's
+inline std::vector<BfvCiphertext> bfv_linear_transform(const std::vector<BfvCiphertext>& cts, const GaloisKeySet& ks,
+                                                       const std::vector<CoeffPoly>& pts) {
+    if (cts.empty()) return {};
+    const BfvParams& prm = *cts[0].params;
+    if (cts[0].c.size() != 2) throw ExactoError(EXACTO_ERR_INVALID_PARAM, "invalid parameter: automorphism requires degree-1 ciphertext");
+    if (pts.size() != ks.size()) throw ExactoError(EXACTO_ERR_INVALID_PARAM, "invalid parameter: one plaintext per element of the key set");
+    auto flat = detail::flatten(cts, 2);
+    std::vector<uint64_t> p(pts.size() * prm.ring_degree), out(flat.size());
+    for (size_t r = 0; r < pts.size(); ++r) {
+        if (pts[r].coeffs.size() != prm.ring_degree) throw ExactoError(EXACTO_ERR_INVALID_PARAM, "invalid parameter: plaintext length");
+        std::copy(pts[r].coeffs.begin(), pts[r].coeffs.end(), p.begin() + r * prm.ring_degree);
+    }
+    detail::check(exacto_bfv_linear_transform(prm.ctx(), ks.handle(), flat.data(), p.data(), out.data(), cts.size()));
+    return detail::unflatten(out, cts.size(), 2, cts[0].params);
+}
+
 // batch_encode + encrypt_sk / encrypt_pk, and decrypt + batch_decode, composed on the device
 inline std::vector<BfvCiphertext> batch_encrypt(const std::vector<SlotVector>& values, const SecretKey* sk,
                                                 const PublicKey* pk, const BfvParamsPtr& prm, ChaChaRng& rng) {

@@ -582,6 +582,59 @@ int exacto_bfv_swap_rows(exacto_ctx* ctx, const uint64_t* ct, size_t polys, cons
                          uint64_t* out, size_t batch);
 int exacto_bfv_swap_rows_dev(exacto_ctx* ctx, const uint64_t* ct, size_t polys, const uint64_t* gk, size_t num_keys,
                              uint64_t* out, size_t batch);
+/* ---- Hoisted rotations and slot linear transforms on a prepared Galois key set ----
+ * R automorphisms of ONE ciphertext share everything that depends on the ciphertext alone: sigma_k is a
+ * ring homomorphism, so sigma_k(c1) == sum_g sigma_k(d_g) B^g with d_g the balanced gadget digits of c1
+ * itself, and in the NTT domain sigma_k only permutes evaluations.  c1 is inverse-transformed, decomposed
+ * and its digits transformed once; each rotation is a multiply-accumulate whose reads go through a table.
+ *
+ * exacto_galois_ntt_permutation (host only, no context): perm[p] = the storage position whose value lands
+ *   at storage position p under sigma_element, NTT(sigma(a))[p] = NTT(a)[perm[p]], in the library's
+ *   NTT-domain order (EXACTO_NTT_ORDER); the same table for every prime.  n: a power of two in 16..16384
+ *   (else InvalidRingDegree); element is taken mod 2n and must be odd: InvalidParam "hoisted automorphisms
+ *   require odd Galois elements" (exacto_bfv_apply_automorphism keeps accepting even ones).
+ *
+ * exacto_galois_keyset_create: elements [R] (host memory in both forms), gks [R][num_keys][2][L][n] (NTT
+ *   domain; host memory, _dev: device memory), key r that of elements[r].  The set keeps on the device the R
+ *   permutation tables and the keys in the form the context's key switch consumes (rows in the 31-bit
+ *   basis, or the keys with their Shoup companions), truncated to min(gadget_digits, num_keys) as the
+ *   single call does; gks may be released when the call returns.  Element 1 is allowed: its key slot is
+ *   never read and its output is a copy of the input; duplicates are allowed.  InvalidParam: R == 0 (or
+ *   above 65535), a null pointer, num_keys == 0 unless every element is 1, an even element.
+ *   The caller owns the set and destroys every set BEFORE destroying the context it was created on.
+ * exacto_galois_keyset_destroy: NULL is a no-op.
+ * exacto_galois_keyset_info: R, the keys used per element, and the 31-bit primes of its key switch (0: the
+ *   limb-wise multiply-accumulate); any out pointer may be NULL.
+ *
+ * exacto_bfv_rotate_hoisted: ct [B][2][L][n] -> out [B][R][2][L][n],
+ *     out[b][r] = (sigma_r(c0) + sum_g sigma_r(d_g) k_{r,g,0}, sum_g sigma_r(d_g) k_{r,g,1})  per limb,
+ *   d_g the digits of the exact CRT of c1 (the decomposition of relinearize; extension semantics for
+ *   Q >= 2^64).  This is NOT bit-identical to exacto_bfv_apply_automorphism, which decomposes sigma(c1):
+ *   the digits of -x are not minus the digits of x where a digit sits at -B/2.  It decrypts to the same
+ *   plaintext under the same noise bound (||sigma(d_g)|| = ||d_g||).
+ * exacto_bfv_linear_transform: pts [R][n] plaintext coefficients shared by the batch (lifted as
+ *   exacto_bfv_plain_mul lifts them), out [B][2][L][n] = sum_r pts[r] * out_hoisted[b][r]: bit for bit the
+ *   composition of exacto_bfv_rotate_hoisted, exacto_bfv_plain_mul and exacto_bfv_add.
+ * Both: out must not overlap ct (InvalidParam); a key set prepared on a context with another n, L, primes or
+ * gadget base (or another key-switch path) is InvalidParam; batch == 0 returns 0.  They run chunk by chunk
+ * (exacto_ctx_set_chunk) with at most R outputs of scratch per chunk item, and leave the state of
+ * exacto_bfv_apply_automorphism untouched. */
+typedef struct exacto_galois_keyset exacto_galois_keyset;
+int exacto_galois_ntt_permutation(size_t n, uint64_t element, uint32_t* perm);
+int exacto_galois_keyset_create(exacto_ctx* ctx, const uint64_t* elements, size_t num_elements, const uint64_t* gks,
+                                size_t num_keys, exacto_galois_keyset** out);
+int exacto_galois_keyset_create_dev(exacto_ctx* ctx, const uint64_t* elements, size_t num_elements, const uint64_t* gks,
+                                    size_t num_keys, exacto_galois_keyset** out);
+void exacto_galois_keyset_destroy(exacto_galois_keyset* ks);
+int exacto_galois_keyset_info(const exacto_galois_keyset* ks, size_t* num_elements, size_t* num_keys_used, int* ks32_primes);
+int exacto_bfv_rotate_hoisted(exacto_ctx* ctx, const exacto_galois_keyset* ks, const uint64_t* ct, uint64_t* out,
+                              size_t batch);
+int exacto_bfv_rotate_hoisted_dev(exacto_ctx* ctx, const exacto_galois_keyset* ks, const uint64_t* ct, uint64_t* out,
+                                  size_t batch);
+int exacto_bfv_linear_transform(exacto_ctx* ctx, const exacto_galois_keyset* ks, const uint64_t* ct,
+                                const uint64_t* pts, uint64_t* out, size_t batch);
+int exacto_bfv_linear_transform_dev(exacto_ctx* ctx, const exacto_galois_keyset* ks, const uint64_t* ct,
+                                    const uint64_t* pts, uint64_t* out, size_t batch);
 /* Compositions on the context's stream, no host round trip: bit for bit exacto_batch_encode followed by
  * exacto_encrypt_sk / exacto_encrypt_pk on the whole batch (values [B][n] instead of pt, the other
  * arguments theirs), and exacto_bfv_decrypt followed by exacto_batch_decode (values_out [B][n]).  The
