@@ -27,22 +27,22 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 VARIANTS = {
     "tensor_pin_both": ({"EXACTO_TENSOR_PIN": "1"}, ["cfg3", "cfg4"]),
     "tensor_pin_none": ({"EXACTO_TENSOR_PIN": "0"}, ["cfg5"]),
-    "ntt_asm_off": ({"EXACTO_NTT_ASM": "0"}, ["cfg3", "cfg5", "hps"]),
-    "ntt_asm_inv_off": ({"EXACTO_NTT_ASM_INV": "0"}, ["cfg3", "cfg5", "hps"]),
+    "ntt_asm_off": ({"EXACTO_NTT_ASM": "0"}, ["cfg3", "cfg5", "hps", "hoist"]),
+    "ntt_asm_inv_off": ({"EXACTO_NTT_ASM_INV": "0"}, ["cfg3", "cfg5", "hps", "hoist"]),
     "ntt_gen_off": ({"EXACTO_NTT_GEN": "0"}, ["hps"]),
     "ntt_genq_off": ({"EXACTO_NTT_GENQ": "0"}, ["hps"]),
     # no asm at all: the special primes then take the C++ rounds too (with NTT_ASM=0 alone they take
     # the generic-prime asm rounds)
-    "ntt_asm_gen_off": ({"EXACTO_NTT_ASM": "0", "EXACTO_NTT_GEN": "0"}, ["cfg3", "hps"]),
-    "one_lane": ({"EXACTO_DUAL_STREAM": "0"}, ["cfg3", "cfg5"]),
-    "three_lanes": ({"EXACTO_LANES": "3"}, ["cfg3"]),
+    "ntt_asm_gen_off": ({"EXACTO_NTT_ASM": "0", "EXACTO_NTT_GEN": "0"}, ["cfg3", "hps", "hoist"]),
+    "one_lane": ({"EXACTO_DUAL_STREAM": "0"}, ["cfg3", "cfg5", "hoist"]),
+    "three_lanes": ({"EXACTO_LANES": "3"}, ["cfg3", "hoist"]),
     "share_ext_off": ({"EXACTO_SHARE_EXT": "0"}, ["cfg4", "cfg5", "hps"]),
-    "digit16_off": ({"EXACTO_DIGIT16": "0"}, ["cfg3", "cfg4"]),
+    "digit16_off": ({"EXACTO_DIGIT16": "0"}, ["cfg3", "cfg4", "hoist"]),
     "digit8_off": ({"EXACTO_DIGIT8": "0"}, ["cfg5", "hps"]),
-    "ks32_off": ({"EXACTO_KS32": "0"}, ["cfg3", "cfg4", "cfg5"]),
+    "ks32_off": ({"EXACTO_KS32": "0"}, ["cfg3", "cfg4", "cfg5", "hoist"]),
     "ks32_wide_off": ({"EXACTO_KS32_WIDE": "0"}, ["cfg4"]),
     "ks32_lazy_off": ({"EXACTO_KS32_LAZY": "0"}, ["cfg3", "cfg4", "cfg5"]),
-    "ks32_wide_primary": ({"EXACTO_KS32_WIDE": "2"}, ["cfg3", "cfg4"]),
+    "ks32_wide_primary": ({"EXACTO_KS32_WIDE": "2"}, ["cfg3", "cfg4", "hoist"]),
     "psum_off": ({"EXACTO_PSUM": "0"}, ["cfg4", "cfg5"]),
     # Garner over P instead of the rounded-float CRT in the SP scale and psum kernels
     "fp_crt_off": ({"EXACTO_FP_CRT": "0"}, ["cfg3", "cfg4", "cfg5"]),
@@ -51,7 +51,7 @@ VARIANTS = {
     "fpq_off": ({"EXACTO_FPQ": "0"}, ["cfg3", "cfg4", "cfg5"]),
     "fpq_band": ({"EXACTO_FPQ": "2"}, ["cfg3", "cfg4", "cfg5"]),
     # ... and in the 31-bit key switch's lift (ks32_crt)
-    "ks_fpc_off": ({"EXACTO_KS_FPC": "0"}, ["cfg3", "cfg4", "cfg5"]),
+    "ks_fpc_off": ({"EXACTO_KS_FPC": "0"}, ["cfg3", "cfg4", "cfg5", "hoist"]),
     # a dBFV batch (dbfv_mul, chain) on one stream instead of two halves (the twin context)
     "chain_split_off": ({"EXACTO_CHAIN_SPLIT": "0"}, ["cfg4", "cfg5", "hps"]),
     "dot30_off": ({"EXACTO_DOT30": "0"}, ["cfg3", "cfg5"]),

@@ -10,6 +10,8 @@ Case groups:
           the chain split over two streams)
   hps     compact_bfv products (one aux prime) and a u64_dbfv dbfv_mul (two aux primes, digit sums)
   polymul the fused NTT product at n = 4096 / 8192, out of place and in place on b
+  hoist   bfv_rotate_hoisted and bfv_linear_transform, cfg3 at n = 4096 (31-bit path) and n = 64 (limb-wise),
+          5 items in chunks of 4, elements [3, 1, 2n - 1]
 """
 
 import hashlib
@@ -27,7 +29,7 @@ from bridge import uniform_residues  # noqa: E402
 from oracle import params as P  # noqa: E402
 from exacto_amd._ffi import HipContext  # noqa: E402
 
-GROUPS = ("cfg3", "cfg4", "cfg5", "hps", "polymul")
+GROUPS = ("cfg3", "cfg4", "cfg5", "hps", "polymul", "hoist")
 
 
 def sha(a) -> str:
@@ -115,6 +117,30 @@ def polymul(out):
         c.synchronize()
         out[f"polymul_{nn}"] = sha(o.cpu().numpy().view(np.uint64))
         out[f"polymul_{nn}_inplace"] = sha(dy.cpu().numpy().view(np.uint64))
+
+
+def hoist_inputs(n):
+    """(params, elements, ct, gks, pts) of the hoist group at ring degree n (tests/test_gpu_hoist_shapes.py
+    rebuilds them for tests/hoist_ref.py)."""
+    prm = P.cfg3_params(n)
+    q = prm.ct_basis.moduli
+    elements = [3, 1, 2 * n - 1]
+    rng = np.random.default_rng(7007 + n)
+    ct = uniform_residues(rng, (5, 2), q, n)
+    gks = uniform_residues(rng, (3, prm.gadget_digits, 2), q, n)
+    pts = rng.integers(0, prm.plain_modulus, size=(3, n), dtype=np.uint64)
+    return prm, elements, ct, gks, pts
+
+
+def hoist(out, sizes=(4096, 64)):
+    for n in sizes:
+        prm, elements, ct, gks, pts = hoist_inputs(n)
+        ctx = HipContext.from_params(prm)
+        ctx.set_chunk(4)
+        ks = ctx.galois_keyset(elements, gks)
+        out[f"hoist_rotate_{n}"] = sha(ctx.bfv_rotate_hoisted(ct, ks))
+        out[f"hoist_lt_{n}"] = sha(ctx.bfv_linear_transform(ct, ks, pts))
+        ks.close()
 
 
 def main():
