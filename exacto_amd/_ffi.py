@@ -156,6 +156,12 @@ _SIGS = [
       for kind in ("sk", "pk") for sfx in ("", "_dev")],
     ("exacto_batch_decrypt", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
     ("exacto_batch_decrypt_dev", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
+    *[(f"exacto_dbfv_batch_{op}{sfx}", [_P, _SZ, _U64, _U64, _P, _P, _SZ], C.c_int)
+      for op in ("encode", "decode") for sfx in ("", "_dev")],
+    *[(f"exacto_dbfv_batch_encrypt_{kind}{sfx}", [_P, _SZ, _U64, _U64, _P, _P, C.c_double, _P, _U64, _P, _SZ], C.c_int)
+      for kind in ("sk", "pk") for sfx in ("", "_dev")],
+    ("exacto_dbfv_batch_decrypt", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
+    ("exacto_dbfv_batch_decrypt_dev", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_plain_mul", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_plain_mul_dev", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_plain_add", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
@@ -1003,6 +1009,75 @@ class HipContext:
 
     def batch_decrypt_dev(self, ct, polys, sk, values, batch):
         check(self._lib.exacto_batch_decrypt_dev(self._h, self._p(ct), polys, self._p(sk), self._p(values), batch))
+
+    # ---- slot-packed dBFV (exacto_dbfv_batch_*): n integers mod p per dBFV ciphertext, exacto_hip.h
+    def dbfv_batch_encode(self, d, base, plain, values) -> np.ndarray:
+        """values [B][n] (reduced mod p; as they are for p = 0) -> pt [B][d][n], row k the slot encoding of the
+        k-th base-b digits."""
+        v = self._batch_rows(values, "values")
+        pt = np.zeros((v.shape[0], d, self.n), dtype=np.uint64)
+        check(self._lib.exacto_dbfv_batch_encode(self._h, d, base, plain, v.ctypes.data, pt.ctypes.data, v.shape[0]))
+        return pt
+
+    def dbfv_batch_decode(self, d, base, plain, pt) -> np.ndarray:
+        """pt [B][d][n] (reduced mod t) -> values [B][n]: slot decode, centre at t/2, recompose mod p."""
+        p = _u64(pt)
+        if p.ndim != 3 or p.shape[1:] != (d, self.n):
+            raise ValueError(f"pt must be a [B][{d}][{self.n}] array")
+        v = np.zeros((p.shape[0], self.n), dtype=np.uint64)
+        check(self._lib.exacto_dbfv_batch_decode(self._h, d, base, plain, p.ctypes.data, v.ctypes.data, p.shape[0]))
+        return v
+
+    def _dbfv_batch_encrypt(self, name, d, base, plain, values, keypoly, key, stream, sigma):
+        k, v, keypoly = self._key(key), self._batch_rows(values, "values"), _u64(keypoly)
+        ct = np.zeros((v.shape[0], d, 2, self.L, self.n), dtype=np.uint64)
+        check(getattr(self._lib, name)(self._h, d, base, plain, v.ctypes.data, keypoly.ctypes.data, sigma,
+                                       k.ctypes.data, stream, ct.ctypes.data, v.shape[0]))
+        return ct
+
+    def dbfv_batch_encrypt_sk(self, d, base, plain, values, sk, key, stream=0, sigma=3.2) -> np.ndarray:
+        """dbfv_batch_encode then encrypt_sk of the B * d plaintexts on the device: values [B][n] ->
+        ct [B][d][2][L][n]."""
+        return self._dbfv_batch_encrypt("exacto_dbfv_batch_encrypt_sk", d, base, plain, values, sk, key, stream, sigma)
+
+    def dbfv_batch_encrypt_pk(self, d, base, plain, values, pk, key, stream=0, sigma=3.2) -> np.ndarray:
+        return self._dbfv_batch_encrypt("exacto_dbfv_batch_encrypt_pk", d, base, plain, values, pk, key, stream, sigma)
+
+    def dbfv_batch_decrypt(self, d, base, plain, ct, sk) -> np.ndarray:
+        """bfv_decrypt of the B * d limbs then dbfv_batch_decode on the device: ct [B][d][2][L][n] -> [B][n]."""
+        ct, sk = _u64(ct), _u64(sk)
+        out = np.zeros((ct.shape[0], self.n), dtype=np.uint64)
+        check(self._lib.exacto_dbfv_batch_decrypt(self._h, d, base, plain, ct.ctypes.data, sk.ctypes.data,
+                                                  out.ctypes.data, ct.shape[0]))
+        return out
+
+    def dbfv_batch_encode_dev(self, d, base, plain, values, pt, batch):
+        check(self._lib.exacto_dbfv_batch_encode_dev(self._h, d, base, plain, self._p(values), self._p(pt), batch))
+
+    def dbfv_batch_decode_dev(self, d, base, plain, pt, values, batch):
+        check(self._lib.exacto_dbfv_batch_decode_dev(self._h, d, base, plain, self._p(pt), self._p(values), batch))
+
+    def dbfv_batch_encrypt_sk_dev(self, d, base, plain, values, sk, key, stream, ct, batch, sigma=3.2):
+        k = self._key(key)
+        check(self._lib.exacto_dbfv_batch_encrypt_sk_dev(self._h, d, base, plain, self._p(values), self._p(sk), sigma,
+                                                         k.ctypes.data, stream, self._p(ct), batch))
+
+    def dbfv_batch_encrypt_pk_dev(self, d, base, plain, values, pk, key, stream, ct, batch, sigma=3.2):
+        k = self._key(key)
+        check(self._lib.exacto_dbfv_batch_encrypt_pk_dev(self._h, d, base, plain, self._p(values), self._p(pk), sigma,
+                                                         k.ctypes.data, stream, self._p(ct), batch))
+
+    def dbfv_batch_decrypt_dev(self, d, base, plain, ct, sk, values, batch):
+        check(self._lib.exacto_dbfv_batch_decrypt_dev(self._h, d, base, plain, self._p(ct), self._p(sk),
+                                                      self._p(values), batch))
+
+    def dbfv_rotate_rows(self, ct, steps, gk) -> np.ndarray:
+        """Both rows of the wide slots left by `steps`: dbfv_apply_automorphism with 3^steps mod 2n and its key."""
+        return self.dbfv_apply_automorphism(ct, galois_element_rotate_rows(self.n, int(steps)), gk)
+
+    def dbfv_swap_rows(self, ct, gk) -> np.ndarray:
+        """The two rows of the wide slots exchanged: dbfv_apply_automorphism with 2n - 1 and its key."""
+        return self.dbfv_apply_automorphism(ct, galois_element_swap_rows(self.n), gk)
 
     def gen_trace_galois_keys(self, sk, key, stream=0, elements=None, sigma=3.2):
         """gen_trace_galois_keys / gen_all_galois_keys (coeffs_to_slots.rs:151-197): one key per element,

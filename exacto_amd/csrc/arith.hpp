@@ -162,3 +162,18 @@ __device__ __forceinline__ u64 signed_mod(i64 v, u64 q, u64 mu64) {
     u64 r = reduce64((u64)(-(v + 1)) + 1u, q, mu64);  // |v| mod q without overflow at INT64_MIN
     return r == 0 ? 0 : q - r;
 }
+
+// The next base-b digit of v (dbfv/decomposition.rs:8-16), v <- floor(v / b).  shift >= 0: b = 2^shift
+// (shift and mask), otherwise a 64-bit divide per digit.
+__device__ __forceinline__ u64 dbfv_digit_next(u64& v, u64 base, int shift) {
+    u64 dg;
+    if (shift >= 0) {
+        dg = v & (base - 1);
+        v >>= shift;
+    } else {
+        const u64 qt = v / base;
+        dg = v - qt * base;
+        v = qt;
+    }
+    return dg;
+}

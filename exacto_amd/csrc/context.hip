@@ -5056,6 +5056,178 @@ extern "C" int exacto_batch_decrypt(exacto_ctx* c, const uint64_t* ct, size_t po
                      [&](std::vector<u64*>& dv, u64* o) { return exacto_batch_decrypt_dev(c, dv[0], polys, dv[1], o, B); });
 }
 
+// ============================================================== slot-packed dBFV (no reference function)
+// n integers mod p per dBFV ciphertext: limb k carries the slot encoding of every slot's k-th digit.  The
+// fused transforms are batch.hip's dbfv_batch_*_kernel; the convention is in include/exacto_hip.h.
+
+// batch_ready's errors, then DbfvParams::new's, then the digit range (dbfv/encrypt.rs:152-159)
+static int dbfv_batch_check(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = batch_ready(c)) return e;
+    if (int e = dbfv_params_check(d, base, plain)) return e;
+    if (base > c->plain)
+        return invalid_param("dBFV base " + std::to_string(base) + " must be <= BFV plaintext modulus " +
+                             std::to_string(c->plain));
+    if (d > (size_t)INT32_MAX / 2) return invalid_param("batch * num_digits too large");
+    return 0;
+}
+
+// values [B][n] and pt [B][d][n]: sizes differ, so any overlap is an error
+static int dbfv_batch_buffers_check(const uint64_t* values, const uint64_t* pt, size_t vwords, size_t d, bool dev) {
+    if (!values || !pt) return invalid_param("dbfv batch: null buffer");
+    if (dev && (((uintptr_t)values | (uintptr_t)pt) & 15))
+        return invalid_param("dbfv batch: buffers must be 16-byte aligned");
+    if (pt < values + vwords && values < pt + vwords * d)
+        return invalid_param("dbfv batch: values and pt overlap (no in-place form)");
+    return 0;
+}
+
+static void dbfv_batch_launch(exacto_ctx* c, bool encode, const u64* in, u64* out, size_t items, size_t d,
+                              uint64_t base, uint64_t plain) {
+    // one grid dimension: 2^31 - 1 items per launch
+    const size_t step = (size_t)1 << 30, n = (size_t)c->n;
+    for (size_t i0 = 0; i0 < items; i0 += step) {
+        const size_t vo = i0 * n, po = i0 * d * n;
+        launch_dbfv_batch(encode, in + (encode ? vo : po), out + (encode ? po : vo), (long)std::min(step, items - i0),
+                          (int)d, base, plain, c->logn, c->batch_tab, c->batch_form, c->stream);
+    }
+}
+
+static int dbfv_batch_transform_dev(exacto_ctx* c, bool encode, size_t d, uint64_t base, uint64_t plain,
+                                    const uint64_t* values, const uint64_t* pt, size_t B) {
+    if (int e = dbfv_batch_check(c, d, base, plain)) return e;
+    if (B == 0) return 0;
+    if (int e = dbfv_batch_buffers_check(values, pt, B * (size_t)c->n, d, true)) return e;
+    dbfv_batch_launch(c, encode, encode ? values : pt, const_cast<u64*>(encode ? pt : values), B, d, base, plain);
+    CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int exacto_dbfv_batch_encode_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                            const uint64_t* values, uint64_t* pt, size_t B) {
+    return dbfv_batch_transform_dev(c, true, d, base, plain, values, pt, B);
+}
+extern "C" int exacto_dbfv_batch_decode_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                            const uint64_t* pt, uint64_t* values, size_t B) {
+    return dbfv_batch_transform_dev(c, false, d, base, plain, values, pt, B);
+}
+
+static int dbfv_batch_transform_host(exacto_ctx* c, bool encode, size_t d, uint64_t base, uint64_t plain,
+                                     const uint64_t* values, const uint64_t* pt, size_t B) {
+    if (int e = dbfv_batch_check(c, d, base, plain)) return e;
+    if (B == 0) return 0;
+    if (int e = dbfv_batch_buffers_check(values, pt, B * (size_t)c->n, d, false)) return e;
+    const size_t vb = B * poly_bytes(c), pb = vb * d;
+    return host_call(c, {{encode ? values : pt, encode ? vb : pb}}, encode ? pb : vb,
+                     const_cast<uint64_t*>(encode ? pt : values), [&](std::vector<u64*>& in, u64* o) {
+                         return dbfv_batch_transform_dev(c, encode, d, base, plain, encode ? in[0] : o,
+                                                         encode ? o : in[0], B);
+                     });
+}
+
+extern "C" int exacto_dbfv_batch_encode(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* values,
+                                        uint64_t* pt, size_t B) {
+    return dbfv_batch_transform_host(c, true, d, base, plain, values, pt, B);
+}
+extern "C" int exacto_dbfv_batch_decode(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* pt,
+                                        uint64_t* values, size_t B) {
+    return dbfv_batch_transform_host(c, false, d, base, plain, values, pt, B);
+}
+
+// encode + encrypt chunk by chunk through batch_buf (d plaintexts per item): limb k of item b keeps the
+// sample indices of item b * d + k of one exacto_encrypt_* call over the [B * d][n] plaintexts
+static int dbfv_batch_encrypt_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* values,
+                                  const uint64_t* sk, const uint64_t* pk, double sigma, const uint64_t* key,
+                                  uint64_t stream, uint64_t* ct, size_t B) {
+    if (int e = dbfv_batch_check(c, d, base, plain)) return e;
+    if (!key || !values || !ct || (!sk && !pk)) return invalid_param("null argument");
+    if (B > (size_t)INT32_MAX / d) return invalid_param("batch * num_digits too large");
+    if (B == 0) return 0;
+    if ((uintptr_t)values & 15) return invalid_param("dbfv batch: buffers must be 16-byte aligned");
+    const size_t C = std::min<size_t>(c->chunk, B), n = (size_t)c->n;
+    if (grow(&c->batch_buf, &c->batch_cap, C * d * poly_bytes(c))) return EXACTO_ERR_HIP;
+    for (size_t i0 = 0; i0 < B; i0 += C) {
+        const size_t cnt = std::min(C, B - i0);
+        dbfv_batch_launch(c, true, values + i0 * n, c->batch_buf, cnt, d, base, plain);
+        CHECK_LAUNCH();
+        if (int e = encrypt_batch(c, c->batch_buf, sk, pk, sigma, key, stream, ct + i0 * d * 2 * c->L * n, cnt * d,
+                                  nullptr, i0 * d))
+            return e;
+    }
+    return 0;
+}
+
+extern "C" int exacto_dbfv_batch_encrypt_sk_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                                const uint64_t* values, const uint64_t* sk, double sigma,
+                                                const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (int e = dbfv_batch_check(c, d, base, plain)) return e;
+    if (!sk) return invalid_param("null argument");
+    return dbfv_batch_encrypt_dev(c, d, base, plain, values, sk, nullptr, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_dbfv_batch_encrypt_pk_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                                const uint64_t* values, const uint64_t* pk, double sigma,
+                                                const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    if (int e = dbfv_batch_check(c, d, base, plain)) return e;
+    if (!pk) return invalid_param("null argument");
+    return dbfv_batch_encrypt_dev(c, d, base, plain, values, nullptr, pk, sigma, key, stream, ct, B);
+}
+
+// decrypt_batch over the chunk's limbs into dig_buf, then the fused decode
+extern "C" int exacto_dbfv_batch_decrypt_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                             const uint64_t* ct, const uint64_t* sk, uint64_t* values, size_t B) {
+    if (int e = dbfv_batch_check(c, d, base, plain)) return e;
+    if (!ct || !sk || !values) return invalid_param("null argument");
+    if (B > (size_t)INT32_MAX / d) return invalid_param("batch * num_digits too large");
+    if (B == 0) return 0;
+    if ((uintptr_t)values & 15) return invalid_param("dbfv batch: buffers must be 16-byte aligned");
+    const size_t C = std::min<size_t>(c->chunk, B), n = (size_t)c->n;
+    const long stride = 2L * c->L * c->n;
+    size_t cap = c->dig_bytes;
+    if (grow(&c->dig_buf, &cap, C * d * poly_bytes(c))) return EXACTO_ERR_HIP;
+    c->dig_bytes = cap;
+    for (size_t i0 = 0; i0 < B; i0 += C) {
+        const size_t cnt = std::min(C, B - i0);
+        if (int e = decrypt_batch(c, ct + i0 * d * (size_t)stride, 2, stride, sk, c->dig_buf, cnt * d)) return e;
+        dbfv_batch_launch(c, false, c->dig_buf, values + i0 * n, cnt, d, base, plain);
+        CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+static int dbfv_batch_encrypt_host(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* values,
+                                   const uint64_t* sk, const uint64_t* pk, double sigma, const uint64_t* key,
+                                   uint64_t stream, uint64_t* ct, size_t B) {
+    if (int e = dbfv_batch_check(c, d, base, plain)) return e;
+    if (!values || !ct || !key || (!sk && !pk)) return invalid_param("null argument");
+    const size_t keyb = (pk ? 2 : 1) * c->L * poly_bytes(c);
+    return host_call(c, {{values, B * poly_bytes(c)}, {pk ? pk : sk, keyb}}, B * d * 2 * c->L * poly_bytes(c), ct,
+                     [&](std::vector<u64*>& in, u64* o) {
+                         return dbfv_batch_encrypt_dev(c, d, base, plain, in[0], pk ? nullptr : in[1],
+                                                       pk ? in[1] : nullptr, sigma, key, stream, o, B);
+                     });
+}
+
+extern "C" int exacto_dbfv_batch_encrypt_sk(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                            const uint64_t* values, const uint64_t* sk, double sigma,
+                                            const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    return dbfv_batch_encrypt_host(c, d, base, plain, values, sk, nullptr, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_dbfv_batch_encrypt_pk(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                            const uint64_t* values, const uint64_t* pk, double sigma,
+                                            const uint64_t* key, uint64_t stream, uint64_t* ct, size_t B) {
+    return dbfv_batch_encrypt_host(c, d, base, plain, values, nullptr, pk, sigma, key, stream, ct, B);
+}
+extern "C" int exacto_dbfv_batch_decrypt(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* ct,
+                                         const uint64_t* sk, uint64_t* values, size_t B) {
+    if (int e = dbfv_batch_check(c, d, base, plain)) return e;
+    if (!ct || !sk || !values) return invalid_param("null argument");
+    if (B == 0) return 0;
+    return host_call(c, {{ct, B * d * 2 * c->L * poly_bytes(c)}, {sk, c->L * poly_bytes(c)}}, B * poly_bytes(c), values,
+                     [&](std::vector<u64*>& in, u64* o) {
+                         return exacto_dbfv_batch_decrypt_dev(c, d, base, plain, in[0], in[1], o, B);
+                     });
+}
+
 // ============================================================== dBFV beyond the product
 // encryption (dbfv/encrypt.rs), limb-wise operations (dbfv/eval.rs:11-71, dbfv/keyswitch.rs,
 // dbfv/advanced.rs:15-29) and the maps between digit vectors (dbfv/advanced.rs:36-160)

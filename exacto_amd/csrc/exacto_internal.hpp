@@ -173,6 +173,12 @@ enum { BF_STRICT = 3 };
 // form: F32_LAZY (t < 2^30), F32_WIDE (t < 2^31) or BF_STRICT; 4 <= logn <= 14
 void launch_batch_transform(bool encode, const u64* in, u64* out, long count, int logn, const BatchTab& tab, int form,
                             hipStream_t s);
+// slot-packed dBFV, one workgroup per item looping over the d digits (base <= t, d >= 1; p = 0: 2^64):
+// encode: values [count][n] -> pt [count][d][n], row k the slot encoding of every slot's k-th base-b digit of
+// the value mod p; otherwise pt [count][d][n] (any u64) -> values [count][n], dbfv_recompose_kernel's signed
+// recomposition mod p of the slot-decoded rows.  in and out must not overlap.
+void launch_dbfv_batch(bool encode, const u64* in, u64* out, long count, int d, u64 base, u64 p, int logn,
+                       const BatchTab& tab, int form, hipStream_t s);
 
 // ---- kernels.hip launchers (all asynchronous on `s`) ----
 struct Operands {            // two degree-1 ciphertext sources, [2][L][n] per item

@@ -144,19 +144,7 @@ void launch_scale_plain(const u64* pt, const u64* delta, u64* dm, long items, in
 // dBFV plaintexts (dbfv/encrypt.rs:105-141 + decomposition.rs:8-16 + bfv/encrypt.rs:181-201) fused:
 // reduce mod p (p == 0: 2^64, taken as is), digit k in base b, times Delta_i mod q_i, written as the
 // Delta*m rows [b * d + k][i][n] of the B * d limb encryptions; the digit plaintexts themselves never
-// exist in memory.  shift >= 0: b = 2^shift (shift and mask), otherwise a 64-bit divide per digit.
-__device__ __forceinline__ u64 dbfv_digit_next(u64& v, u64 base, int shift) {
-    u64 dg;
-    if (shift >= 0) {
-        dg = v & (base - 1);
-        v >>= shift;
-    } else {
-        const u64 qt = v / base;
-        dg = v - qt * base;
-        v = qt;
-    }
-    return dg;
-}
+// exist in memory.  The digits are peeled by dbfv_digit_next (arith.hpp).
 
 // Scalar plaintexts: the digit polynomial is a constant, whose NTT is that constant in every slot
 // (as trivial_const_kernel), so the rows are written in the NTT domain.  One block per row chunk:

@@ -1375,6 +1375,92 @@ inline DbfvCiphertext dbfv_apply_automorphism(const DbfvCiphertext& ct, const Ga
     return detail::make_dbfv(out, d, 2, ct.degree, ct.mul_depth, ct.params);
 }
 
+// ---- slot-packed dBFV (exacto_dbfv_batch_*, no reference function): n integers mod p per ciphertext, limb k
+// carrying the slot encoding of the k-th digits; plain_modulus = 0 (2^64) is allowed.  Needs a batching prime t.
+// A dBFV plaintext of the slot form: d polynomials mod t.
+using DbfvSlotPlain = std::vector<CoeffPoly>;
+
+inline DbfvSlotPlain dbfv_batch_encode(const SlotVector& values, const DbfvParamsPtr& params) {
+    const DbfvParams& dp = *params;
+    const BfvParams& prm = *dp.bfv_params;
+    const size_t n = prm.ring_degree, d = dp.num_digits;
+    if (values.size() != n)
+        throw ExactoError(2, "dimension mismatch: expected " + std::to_string(n) + ", got " + std::to_string(values.size()));
+    std::vector<uint64_t> out(d * n);
+    detail::check(exacto_dbfv_batch_encode(prm.ctx(), d, dp.base, dp.plain_modulus, values.data(), out.data(), 1));
+    DbfvSlotPlain res(d);
+    for (size_t k = 0; k < d; ++k) {
+        res[k].coeffs.assign(out.begin() + (long)(k * n), out.begin() + (long)((k + 1) * n));
+        res[k].modulus = prm.plain_modulus;
+    }
+    return res;
+}
+inline SlotVector dbfv_batch_decode(const DbfvSlotPlain& pt, const DbfvParamsPtr& params) {
+    const DbfvParams& dp = *params;
+    const BfvParams& prm = *dp.bfv_params;
+    const size_t n = prm.ring_degree, d = dp.num_digits;
+    if (pt.size() != d) throw ExactoError(1, "invalid parameter: expected d digit plaintexts");
+    std::vector<uint64_t> flat;
+    for (auto& p : pt) {
+        if (p.coeffs.size() != n)
+            throw ExactoError(2, "dimension mismatch: expected " + std::to_string(n) + ", got " +
+                                     std::to_string(p.coeffs.size()));
+        flat.insert(flat.end(), p.coeffs.begin(), p.coeffs.end());
+    }
+    SlotVector out(n);
+    detail::check(exacto_dbfv_batch_decode(prm.ctx(), d, dp.base, dp.plain_modulus, flat.data(), out.data(), 1));
+    return out;
+}
+namespace detail {
+inline DbfvCiphertext dbfv_batch_encrypt_any(const SlotVector& values, const SecretKey* sk, const PublicKey* pk,
+                                             const DbfvParamsPtr& params, ChaChaRng& rng) {
+    const DbfvParams& dp = *params;
+    const BfvParams& prm = *dp.bfv_params;
+    const size_t d = dp.num_digits;
+    if (values.size() != prm.ring_degree)
+        throw ExactoError(2, "dimension mismatch: expected " + std::to_string(prm.ring_degree) + ", got " +
+                                 std::to_string(values.size()));
+    std::vector<uint64_t> ct(d * 2 * limb_words(dp));
+    std::vector<uint64_t> pkf;
+    if (pk) {
+        pkf = pk->pk0.data;
+        pkf.insert(pkf.end(), pk->pk1.data.begin(), pk->pk1.data.end());
+    }
+    check((sk ? exacto_dbfv_batch_encrypt_sk : exacto_dbfv_batch_encrypt_pk)(
+        prm.ctx(), d, dp.base, dp.plain_modulus, values.data(), sk ? sk->poly.data.data() : pkf.data(), prm.sigma,
+        rng.key, rng.next(), ct.data(), 1));
+    return make_dbfv(ct, d, 2, d, 0, params);
+}
+}  // namespace detail
+inline DbfvCiphertext dbfv_batch_encrypt_sk(const SlotVector& values, const SecretKey& sk, const DbfvParamsPtr& params,
+                                            ChaChaRng& rng) {
+    return detail::dbfv_batch_encrypt_any(values, &sk, nullptr, params, rng);
+}
+inline DbfvCiphertext dbfv_batch_encrypt_pk(const SlotVector& values, const PublicKey& pk, const DbfvParamsPtr& params,
+                                            ChaChaRng& rng) {
+    return detail::dbfv_batch_encrypt_any(values, nullptr, &pk, params, rng);
+}
+inline SlotVector dbfv_batch_decrypt(const DbfvCiphertext& ct, const SecretKey& sk) {
+    const DbfvParams& dp = *ct.params;
+    auto flat = detail::flatten_dbfv(ct);
+    SlotVector out(dp.bfv_params->ring_degree);
+    detail::check(exacto_dbfv_batch_decrypt(dp.bfv_params->ctx(), dp.num_digits, dp.base, dp.plain_modulus, flat.data(),
+                                            sk.poly.data.data(), out.data(), 1));
+    return out;
+}
+// Both rows of the wide slots left by `steps` (gk: the key of galois_element_rotate_rows(n, steps)) / exchanged
+// (gk: the key of galois_element_swap_rows(n)): dbfv_apply_automorphism with that element.
+inline DbfvCiphertext dbfv_rotate_rows(const DbfvCiphertext& ct, int64_t steps, const GaloisKey& gk) {
+    if (gk.element != galois_element_rotate_rows(ct.params->bfv_params->ring_degree, steps))
+        throw ExactoError(1, "invalid parameter: the Galois key is not that of this rotation");
+    return dbfv_apply_automorphism(ct, gk);
+}
+inline DbfvCiphertext dbfv_swap_rows(const DbfvCiphertext& ct, const GaloisKey& gk) {
+    if (gk.element != galois_element_swap_rows(ct.params->bfv_params->ring_degree))
+        throw ExactoError(1, "invalid parameter: the Galois key is not that of the row swap");
+    return dbfv_apply_automorphism(ct, gk);
+}
+
 // dbfv_div_by_base (src/dbfv/advanced.rs:36-93): the result carries new DbfvParams with p / base.
 inline DbfvCiphertext dbfv_div_by_base(const DbfvCiphertext& ct) {
     const DbfvParams& dp = *ct.params;

@@ -653,6 +653,67 @@ int exacto_batch_decrypt(exacto_ctx* ctx, const uint64_t* ct, size_t polys, cons
 int exacto_batch_decrypt_dev(exacto_ctx* ctx, const uint64_t* ct, size_t polys, const uint64_t* sk,
                              uint64_t* values_out, size_t batch);
 
+/* ---- Slot-packed dBFV: n integers mod p per dBFV ciphertext (no reference function) ----
+ * Slot encoding is a ring isomorphism R_t = Z_t^n, and dbfv_mul / dbfv_square / dbfv_add / dbfv_sub /
+ * dbfv_neg / dbfv_relinearize, the reduction with the small representatives, dbfv_div_by_base and
+ * dbfv_change_base are Z-linear combinations of BFV products of limbs, so each acts on every slot
+ * independently: a dBFV ciphertext [d][2][L][n] whose limb k encrypts the slot encoding of the k-th digits
+ * of n values carries n independent integers mod p through all of them, and exacto_dbfv_apply_automorphism
+ * with exacto_galois_element_rotate_rows / _swap_rows moves them as it moves BFV slots.  A constant
+ * polynomial is "all slots equal", so the digit growth per slot is that of the SCALAR dBFV case, not the
+ * n times larger growth of the polynomial case: the scalar bound on t is enough (one product at the u64
+ * profile, b = 256, d = 8: t > 2 d (b - 1)^2 = 1040400), and t must be a batching prime, t == 1 (mod 2n),
+ * t < 2^32 (the smallest for the u64 profile: 1073153 at n = 4096, 1097729 at n = 8192).
+ * dbfv_plain_modulus = 0 (p = 2^64) is ALLOWED in all of these calls: the polynomial entry points reject it
+ * as "scalar-only" because a polynomial product mixes coefficients, whereas here every slot is a scalar
+ * of its own and wrapping 64-bit arithmetic per slot is exactly dBFV's scalar case.
+ *
+ * exacto_dbfv_batch_encode: values [B][n] -> pt [B][d][n].  values[b][s] is reduced mod p (taken as is for
+ *   p = 2^64, as exacto_dbfv_encrypt_sk does; the host form does not reject, it reduces like the _dev form),
+ *   decomposed into d base-b digits (decomposition.rs:8-16, excess digits dropped), and pt[b][k] is the slot
+ *   encoding (exacto_batch_encode's: the same zeta, the same slot matrix) of the vector of k-th digits.
+ * exacto_dbfv_batch_decode: pt [B][d][n] -> values [B][n].  Every pt[b][k] (any u64, reduced mod t) is slot
+ *   decoded, centred at floor(t / 2) and recomposed as sum_k centred_k b^k in i128 with wrapping, then mod p
+ *   (p = 2^64: truncation): the arithmetic of exacto_dbfv_decrypt_poly, slot by slot.
+ * exacto_dbfv_batch_encrypt_sk / _pk: ct [B][d][2][L][n]; limb k of item b is bit for bit item b*d + k of
+ *   exacto_encrypt_sk / exacto_encrypt_pk called with the same (key, stream, sigma) on the [B*d][n]
+ *   plaintexts of exacto_dbfv_batch_encode (the guarantee of exacto_dbfv_encrypt_*).  Chunk by chunk
+ *   (exacto_ctx_set_chunk) through a context-owned plaintext buffer of d polynomials per chunk item.
+ * exacto_dbfv_batch_decrypt: ct [B][d][2][L][n] -> values_out [B][n]: exacto_bfv_decrypt of the B*d limbs,
+ *   then exacto_dbfv_batch_decode, chunk by chunk.
+ * One fused kernel per direction (batch.hip): one workgroup per item loops over the d digits, so the digit
+ * vectors [B][d][n] never exist in memory.
+ * Errors, all before any launch and in this order: the context's batching error (above); those of
+ * DbfvParams::new ("base must be >= 2", "num_digits must be >= 1", "base^digits = {b^d} < plain_modulus =
+ * {p}"); InvalidParam "dBFV base {b} must be <= BFV plaintext modulus {t}".  Also InvalidParam: a null
+ * pointer, a _dev values / pt buffer that is not 16-byte aligned, any overlap of values and pt (their
+ * sizes differ: there is no in-place form).  batch == 0 returns 0.  The _dev forms are asynchronous on the
+ * context's stream, apart from the one wait of a context's first batching call. */
+int exacto_dbfv_batch_encode(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                             const uint64_t* values, uint64_t* pt, size_t batch);
+int exacto_dbfv_batch_encode_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                 const uint64_t* values, uint64_t* pt, size_t batch);
+int exacto_dbfv_batch_decode(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                             const uint64_t* pt, uint64_t* values, size_t batch);
+int exacto_dbfv_batch_decode_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                 const uint64_t* pt, uint64_t* values, size_t batch);
+int exacto_dbfv_batch_encrypt_sk(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                 const uint64_t* values, const uint64_t* sk, double sigma, const uint64_t* key,
+                                 uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_dbfv_batch_encrypt_sk_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                     const uint64_t* values, const uint64_t* sk, double sigma, const uint64_t* key,
+                                     uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_dbfv_batch_encrypt_pk(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                 const uint64_t* values, const uint64_t* pk, double sigma, const uint64_t* key,
+                                 uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_dbfv_batch_encrypt_pk_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                     const uint64_t* values, const uint64_t* pk, double sigma, const uint64_t* key,
+                                     uint64_t stream, uint64_t* ct, size_t batch);
+int exacto_dbfv_batch_decrypt(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                              const uint64_t* ct, const uint64_t* sk, uint64_t* values_out, size_t batch);
+int exacto_dbfv_batch_decrypt_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                  const uint64_t* ct, const uint64_t* sk, uint64_t* values_out, size_t batch);
+
 /* Plaintext-ciphertext operations (CoeffsToSlots' linear layer), all in the NTT domain.
  * ct/out [B][polys][L][n]; pt [B][n] plaintext coefficients (any u64, reduced mod each q_i).
  *   bfv_plain_mul     replaces bfv::eval::bfv_plain_mul      (src/bfv/eval.rs:468-486)
