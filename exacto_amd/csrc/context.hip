@@ -20,6 +20,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/exacto_hip.h"
@@ -188,6 +189,55 @@ struct ProfRec {
     const void* kern;   // host handle of the last kernel launched inside the scope (EXACTO_LAUNCH)
 };
 
+static void free_dev(void* p);
+static hipError_t dev_alloc(void** p, size_t bytes);
+
+// A device buffer that owns its memory.  Move-only; released through free_dev when its owner goes, so
+// every release reaches the EXACTO_DEBUG_ALLOC log.  It converts to its pointer, so the launchers take
+// it as they took the raw pointer; nothing outside the type assigns the pointer or the capacity.
+template <class T>
+class DevBuf {
+    T* p_ = nullptr;
+    size_t cap_ = 0;   // bytes
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.p_; cap_ = o.cap_;
+            o.p_ = nullptr; o.cap_ = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    operator T*() const { return p_; }
+    T* get() const { return p_; }
+    size_t bytes() const { return cap_; }
+    void reset() {
+        free_dev(p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    // exactly `bytes` (the tables allocated once, the workspaces): what it held is released first
+    int alloc(size_t bytes) {
+        reset();
+        HIP_TRY(dev_alloc((void**)&p_, bytes));
+        cap_ = bytes;
+        return 0;
+    }
+    // at least max(bytes, 8): nothing when the capacity suffices, else free first, then allocate (the
+    // old and the new block are never live together).  A failure leaves the buffer empty.
+    int grow(size_t bytes) {
+        bytes = std::max<size_t>(bytes, 8);
+        return cap_ >= bytes ? 0 : alloc(bytes);
+    }
+};
+static_assert(!std::is_copy_constructible<DevBuf<u64>>::value && !std::is_copy_assignable<DevBuf<u64>>::value,
+              "a device buffer has one owner");
+
 // A 31-bit auxiliary basis of the ks32 key switch (ks32.hip) with its device tables and the
 // relinearisation key converted to it.
 struct Ks32Basis {
@@ -197,12 +247,25 @@ struct Ks32Basis {
     int mac_form = 0;             // ks32_mac: 0 primes up to 2^31 (7 products per reduction),
                                   // 1 below 2^32 / 3 (12), 2 below 2^30 (12, lazy transforms)
     Big P;                        // product of the primes
-    Prime32* d_p32 = nullptr;
-    uint2* d_tw32 = nullptr;
-    Ks32Tables* d_kst = nullptr;
-    uint32_t* d_rs = nullptr;     // the relinearisation key in this basis
-    size_t rs_cap = 0;
+    DevBuf<Prime32> d_p32;
+    DevBuf<uint2> d_tw32;
+    DevBuf<Ks32Tables> d_kst;
+    DevBuf<uint32_t> d_rs;        // the relinearisation key in this basis
     bool rs_valid = false;
+};
+static_assert(!std::is_copy_constructible<Ks32Basis>::value && !std::is_copy_assignable<Ks32Basis>::value,
+              "a basis owns its tables");
+
+// The per-chunk workspace of one pipeline lane, sized in items (products) by ensure().
+struct exacto_ctx;
+struct Workspace {
+    size_t items = 0;
+    DevBuf<u64> coefQ, extP, T, D;
+    // exact path with gadget base <= 2^16: the scale kernel writes each digit once as int16 and
+    // the digit NTT converts it per limb on load (EXACTO_DIGIT16=0: u64 digits per limb)
+    DevBuf<int16_t> D16;
+    DevBuf<uint32_t> DS, U;   // ks32: digit residues [item][G][S][n] and accumulators [item][2L][S][n]
+    int ensure(const exacto_ctx* c, size_t want);
 };
 
 // Stream and per-chunk workspace of one extra pipeline lane (lane 0 is the context's own).
@@ -210,10 +273,7 @@ constexpr int EXACTO_MAX_LANES = 4;
 struct LaneSet {
     hipStream_t stream = nullptr;
     hipEvent_t join = nullptr;
-    size_t items = 0;
-    u64 *coefQ = nullptr, *extP = nullptr, *T = nullptr, *D = nullptr;
-    int16_t* D16 = nullptr;
-    uint32_t *DS = nullptr, *U = nullptr;
+    Workspace ws;
 };
 
 struct exacto_ctx {
@@ -227,14 +287,14 @@ struct exacto_ctx {
     int path = EXACTO_PATH_EXACT_RNS;
     int deferred_code = 0;  // error raised at multiplication time (reference semantics)
     std::string deferred_msg;
-    PrimeConst* d_primes = nullptr;
-    TwPair* d_tw = nullptr;
-    CrtTables* d_crt = nullptr;
+    DevBuf<PrimeConst> d_primes;
+    DevBuf<TwPair> d_tw;
+    DevBuf<CrtTables> d_crt;
     CrtTables h_crt{};
-    u64* d_scal = nullptr;
-    u64* d_rlk = nullptr;
-    u64* d_rlk_s = nullptr;  // Shoup companions of the key (limb-wise relinearisation MAC)
-    size_t rlk_keys = 0, rlk_cap = 0, rlk_s_cap = 0;
+    DevBuf<u64> d_scal;
+    DevBuf<u64> d_rlk;
+    DevBuf<u64> d_rlk_s;  // Shoup companions of the key (limb-wise relinearisation MAC)
+    size_t rlk_keys = 0;
     bool rlk_s_valid = false;
     // EXACTO_NTT_ASM=0: no special-prime (2^60 - d) asm rounds; those batches then take the generated
     // generic-prime asm rounds where their size has them (n = 1024 / 4096 / 8192, lazy primes), and the
@@ -269,7 +329,8 @@ struct exacto_ctx {
     // the auxiliary primes into ext_a and transformed both in one launch; the next step's extension of
     // its left operand is then already in ext_a (measured A/B: DESIGN.md §6.4)
     bool ext_a_ready = false;
-    int16_t* ks_defer = nullptr;  // run_mul: int16 digits of product p to ks_defer + p G n, no key switch
+    // (a view of d_dall, not owned) run_mul: int16 digits of product p to ks_defer + p G n, no key switch
+    int16_t* ks_defer = nullptr;
     bool ks_defer8 = false;       // ... int8 digits instead (base <= 2^8; EXACTO_DIGIT8=0: int16)
     bool digit8_env = true;
     // dBFV psum (EXACTO_PSUM=0: off): an output limb's c0 / c1 scaled once from the sum of its
@@ -295,31 +356,24 @@ struct exacto_ctx {
         int d = 0, npairs = 0;
         const int* term_start = nullptr;
         const CombineTerm* terms = nullptr;
-        u64* out = nullptr;       // [B][d][2][L][n], coefficient domain
+        u64* out = nullptr;       // [B][d][2][L][n], coefficient domain (a view: the caller's buffer)
         bool fpc = false;         // its scale may take the rounded-float CRT over P (m <= psum_fp_max)
     } psum;
-    u64* d_hdig = nullptr;       // dBFV over HPS: the summed digits' NTT residues [B][d][G][L][n]
-    size_t hdig_cap = 0;
-    int16_t* d_dall = nullptr;   // dBFV: per-product digits
-    void* d_dk = nullptr;        // ... and their per-limb sums (int16, or int32 when m ceil(B/2) > 2^15 - 1)
-    uint32_t *d_dsk = nullptr, *d_uk = nullptr;   // their residues and key-switch sums in the 31-bit basis
-    size_t dall_cap = 0, dk_cap = 0, dsk_cap = 0, uk_cap = 0;
+    DevBuf<u64> d_hdig;          // dBFV over HPS: the summed digits' NTT residues [B][d][G][L][n]
+    DevBuf<int16_t> d_dall;      // dBFV: per-product digits
+    DevBuf<void> d_dk;           // ... and their per-limb sums (int16, or int32 when m ceil(B/2) > 2^15 - 1)
+    DevBuf<uint32_t> d_dsk, d_uk;   // their residues and key-switch sums in the 31-bit basis
+    // views of the active basis' tables (use_ks32_basis): kn / kz own them
     Prime32* d_p32 = nullptr;
     uint2* d_tw32 = nullptr;
     Ks32Tables* d_kst = nullptr;
-    uint32_t* d_rs = nullptr;    // key in the auxiliary basis [keys][2L][S][n], NTT domain mod p_s
-    size_t rs_cap = 0;
+    DevBuf<uint32_t> d_rs;       // key in the auxiliary basis [keys][2L][S][n], NTT domain mod p_s
     bool rs_valid = false;
-    uint32_t *ws_DS = nullptr, *ws_U = nullptr;
     bool rlk_loaded = false;
-    // workspace (per chunk)
+    // workspace (per chunk) of lane 0
     size_t chunk = 512;  // products per pipeline pass; throughput plateaus from ~512 (r1 sweep)
-    size_t ws_items = 0;
-    u64 *ws_coefQ = nullptr, *ws_extP = nullptr, *ws_T = nullptr, *ws_D = nullptr;
-    // exact path with gadget base <= 2^16: the scale kernel writes each digit once as int16 and
-    // the digit NTT converts it per limb on load (EXACTO_DIGIT16=0: u64 digits per limb)
-    bool digit16 = true;
-    int16_t* ws_D16 = nullptr;
+    Workspace ws;
+    bool digit16 = true;   // EXACTO_DIGIT16=0: u64 digits per limb instead of Workspace::D16
     // further pipeline lanes: chunk i runs on lane i % lanes, each lane a stream with its own
     // workspace, so the kernels of consecutive chunks overlap (EXACTO_DUAL_STREAM=0: one lane;
     // EXACTO_LANES: lane count, 2 by default)
@@ -339,61 +393,45 @@ struct exacto_ctx {
     // (EXACTO_SHARE_EXT=0 recomputes them per product)
     bool share_ext = true;
     // keygen / encryption
-    double* d_cdt = nullptr;
-    size_t cdt_cap = 0;
+    DevBuf<double> d_cdt;
     double cdt_sigma = 0.0;
-    u64* d_gpow = nullptr;
-    size_t gpow_cap = 0;
-    u64* d_delta = nullptr;
+    DevBuf<u64> d_gpow;
+    DevBuf<u64> d_delta;
     bool delta_ok = false;
-    u64* enc_buf = nullptr;
-    size_t enc_cap = 0;
-    u64* d_lin = nullptr;  // terms of the last dBFV linear map, LinTerm [E][L]
-    size_t lin_cap = 0;
+    DevBuf<u64> enc_buf;
+    DevBuf<u64> d_lin;  // terms of the last dBFV linear map, LinTerm [E][L]
     std::vector<u64> lin_host;  // what d_lin holds
-    u64* gk_s = nullptr;  // Shoup companions of the Galois key of the last automorphism call
-    size_t gk_s_cap = 0;
-    uint32_t* d_gk_rs = nullptr;  // ks32: Galois key of the last automorphism call in the 31-bit basis
-    size_t gk_rs_cap = 0;
-    u64* pl_buf = nullptr;  // lifted plaintexts / monomial scratch
-    size_t pl_cap = 0;
-    u64 *ext_a = nullptr, *ext_b = nullptr;
-    size_t ext_a_cap = 0, ext_b_cap = 0;
-    u64* chain_buf = nullptr;  // dBFV chain ping-pong buffers
-    size_t chain_bytes = 0;
+    DevBuf<u64> gk_s;  // Shoup companions of the Galois key of the last automorphism call
+    DevBuf<uint32_t> d_gk_rs;  // ks32: Galois key of the last automorphism call in the 31-bit basis
+    DevBuf<u64> pl_buf;  // lifted plaintexts / monomial scratch
+    DevBuf<u64> ext_a, ext_b;
+    DevBuf<u64> chain_buf;  // dBFV chain ping-pong buffers
     // dBFV chain, psum path: each step's relinearised limbs also in the coefficient domain (they are
     // there before the final forward NTT), so the next step's extension lifts them directly instead
     // of inverse-transforming its NTT-domain input (dbfv_mul_group, exacto_dbfv_mul_chain_dev)
-    u64* chain_coef = nullptr;
-    size_t chain_coef_bytes = 0;
+    DevBuf<u64> chain_coef;
+    // (coef_out and coef_in are views into chain_coef halves, not owned)
     u64* coef_out = nullptr;        // where this step's coefficient form went (psum steps of a chain)
     int coef_slot = -1;             // set by the chain: chain_coef half for this step's coefficient form
     size_t coef_slot_words = 0;     // ... and the size of one half
     const u64* coef_in = nullptr;   // set by the chain: the coefficient form of this step's `a`
     bool coef_written = false;      // reported back: coef_out holds this step's results
-    u64* dec_buf = nullptr;    // decryption phase [B][L][n]
-    size_t dec_bytes = 0;
-    u64* dig_buf = nullptr;    // dBFV decrypted digits [B][d][n]
-    size_t dig_bytes = 0;
+    DevBuf<u64> dec_buf;    // decryption phase [B][L][n]
+    DevBuf<u64> dig_buf;    // dBFV decrypted digits [B][d][n]
     // staging for host-pointer API and dBFV products
-    u64* io = nullptr;
-    size_t io_bytes = 0;
-    u64* prod = nullptr;
-    size_t prod_bytes = 0;
+    DevBuf<u64> io;
+    DevBuf<u64> prod;
     // product-sum plan cache (dbfv_mul's index rule, or bfv_mul_sum's term lists: cached_kind)
-    u64* d_off = nullptr;
-    size_t off_cap = 0;
+    DevBuf<u64> d_off;
     int cached_kind = -1;            // 0: dbfv_plan, 1: mul_sum_plan, 2: dbfv_plan's symmetric form; -1: none
     std::vector<uint32_t> cached_ms; // mul_sum_plan: ia, ib, slot lists, then na, nb, nslots, group limit
     int cached_ngroups = 0;          // mul_sum_plan: groups of the cached plan (its "output limbs")
-    int* d_slot_start = nullptr;     // ... and, when a slot has several, slot s = groups [start[s], start[s+1])
-    u64* gsum_buf = nullptr;         // bfv_mul_sum: the groups' coefficient-domain results [B][groups][2][L][n]
-    size_t gsum_cap = 0;
+    DevBuf<int> d_slot_start;        // ... and, when a slot has several, slot s = groups [start[s], start[s+1])
+    DevBuf<u64> gsum_buf;            // bfv_mul_sum: the groups' coefficient-domain results [B][groups][2][L][n]
     // modulus switch: q_j^-1 mod q_i (j > i) at [j * L + i] with their Shoup companions, built on first use;
     // the intermediate levels of a call that drops several primes (two halves, one chunk each)
     std::vector<u64> msw_w, msw_ws;
-    u64* msw_buf = nullptr;
-    size_t msw_cap = 0;
+    DevBuf<u64> msw_buf;
     // SIMD batching (batch.hip): validated and built at the context's first batching call (batch_ready)
     int batch_state = 0;             // 0: not tried, 1: tables resident, -1: this context cannot batch
     int batch_code = 0;              // ... and why
@@ -401,26 +439,22 @@ struct exacto_ctx {
     u64 batch_root = 0;              // zeta = find_psi(n, t)
     int batch_form = 0;              // the transforms' arithmetic (F32_LAZY / F32_WIDE / BF_STRICT)
     BatchTab batch_tab{};
-    uint2* d_btw = nullptr;          // [2][n] forward, inverse twiddles mod t
-    uint32_t* d_bperm = nullptr;     // [n] slot -> storage position
-    u64* batch_buf = nullptr;        // the compositions' plaintexts, one chunk
-    size_t batch_cap = 0;
+    DevBuf<uint2> d_btw;             // [2][n] forward, inverse twiddles mod t
+    DevBuf<uint32_t> d_bperm;        // [n] slot -> storage position
+    DevBuf<u64> batch_buf;           // the compositions' plaintexts, one chunk
     size_t cached_B = 0, cached_d = 0;
     u64 cached_base = 0, cached_p = 0;
     int cached_npairs = 0;
     std::vector<int> cached_limbs;   // output limbs of the cached plan (all d, or a subset: exacto_dbfv_mul_limbs)
     int cached_sum_m = 0;        // max products per dBFV output limb when all combine terms are sums, else -1
-    int* d_term_start = nullptr;
-    CombineTerm* d_terms = nullptr;
-    size_t terms_cap = 0;
+    DevBuf<int> d_term_start;
+    DevBuf<CombineTerm> d_terms;
     // per-call scratch: the context's own stream-ordered pool (Scratch)
     hipMemPool_t pool = nullptr;
     // the bootstrap's intermediates (coefficients, flags, the c0'/c1' rows, phase, slots): a persistent
     // buffer of the boot context, grown like the workspaces, never from the stream-ordered pool
-    u64* boot_buf = nullptr;
-    size_t boot_cap = 0;
-    u64* boot_slots = nullptr;   // ... and the slots of the ring path, grown when an item takes it
-    size_t boot_slots_cap = 0;
+    DevBuf<u64> boot_buf;
+    DevBuf<u64> boot_slots;      // ... and the slots of the ring path, grown when an item takes it
     bool debug_scratch = false;
     size_t dbfv_group_bytes = (size_t)16384 << 20;  // dbfv_mul item groups (EXACTO_DBFV_GROUP_MB)
     // profiling
@@ -514,16 +548,6 @@ static hipError_t dev_alloc(void** p, size_t bytes) {
 static hipError_t dev_copy(void* dst, const void* src, size_t bytes, hipStream_t s) {
     launch_copy_u64(static_cast<u64*>(dst), static_cast<const u64*>(src), (long)(bytes / 8), s);
     return hipGetLastError();
-}
-
-static int grow(u64** buf, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return 0;
-    free_dev(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(dev_alloc((void**)buf, bytes));
-    *cap = bytes;
-    return 0;
 }
 
 // Host -> device copy ordered on the context stream.  The stream is non-blocking, so it does not
@@ -684,13 +708,13 @@ static int build_ks32_basis_impl(exacto_ctx* c, u64 pmax, u64 qmax, const Big& b
         Q.flast_ws = sh32(flw, p);
         Q.inv_p = 1.0 / (double)p;
     }
-    HIP_TRY(dev_alloc((void**)&b->d_tw32, tw.size() * sizeof(uint2)));
+    if (int e_ = b->d_tw32.alloc(tw.size() * sizeof(uint2))) return e_;
     if (int e_ = upload(c, b->d_tw32, tw.data(), tw.size() * sizeof(uint2))) return e_;
     for (int s = 0; s < S; ++s) {
         pc[s].tw_fwd = b->d_tw32 + (size_t)s * 2 * n;
         pc[s].tw_inv = b->d_tw32 + (size_t)s * 2 * n + n;
     }
-    HIP_TRY(dev_alloc((void**)&b->d_p32, S * sizeof(Prime32)));
+    if (int e_ = b->d_p32.alloc(S * sizeof(Prime32))) return e_;
     if (int e_ = upload(c, b->d_p32, pc.data(), S * sizeof(Prime32))) return e_;
     Ks32Tables T;
     std::memset(&T, 0, sizeof(T));
@@ -729,7 +753,7 @@ static int build_ks32_basis_impl(exacto_ctx* c, u64 pmax, u64 qmax, const Big& b
         T.fpc_n[l][0] = (uint32_t)(T.negP[l] & M30);
         T.fpc_n[l][1] = (uint32_t)(T.negP[l] >> 30);
     }
-    HIP_TRY(dev_alloc((void**)&b->d_kst, sizeof(Ks32Tables)));
+    if (int e_ = b->d_kst.alloc(sizeof(Ks32Tables))) return e_;
     if (int e_ = upload(c, b->d_kst, &T, sizeof(Ks32Tables))) return e_;
     b->S = S;
     return 0;
@@ -747,16 +771,10 @@ static void use_ks32_basis(exacto_ctx* c, const Ks32Basis& b) {
     c->ks32_lazy_active = &b == &c->kz;
 }
 
-static void free_basis(Ks32Basis* b) {
-    free_dev(b->d_p32); free_dev(b->d_tw32); free_dev(b->d_kst); free_dev(b->d_rs);
-    *b = Ks32Basis{};
-}
-
-// build_ks32_basis_impl, releasing whatever it allocated when a later step fails (the basis is not
-// attached to the context yet, so exacto_ctx_destroy would not free it)
+// build_ks32_basis_impl, releasing whatever it allocated when a later step fails (no half-built basis)
 static int build_ks32_basis(exacto_ctx* c, u64 pmax, u64 qmax, const Big& bound, Ks32Basis* b, int fixedS = 0) {
     const int e = build_ks32_basis_impl(c, pmax, qmax, bound, b, fixedS);
-    if (e) free_basis(b);
+    if (e) *b = Ks32Basis{};
     return e;
 }
 
@@ -789,23 +807,20 @@ static int setup_ks32(exacto_ctx* c) {
     Ks32Basis prim;
     if (int e = build_ks32_basis(c, wide_mode == 2 ? (1ull << 31) : (1ull << 32) / 3, qmax, bound, &prim)) return e;
     if (wide_mode == 1) {
-        if (int e = build_ks32_basis(c, 1ull << 31, qmax, bound, &c->kw)) {
-            free_basis(&prim);
-            return e;
-        }
+        if (int e = build_ks32_basis(c, 1ull << 31, qmax, bound, &c->kw)) return e;
         if (prim.S == 0 && c->kw.S > 0) {   // only the wide range holds the bound: it is the primary
-            prim = c->kw;
+            prim = std::move(c->kw);
             c->kw = Ks32Basis{};
         } else if (c->kw.S > 0 && c->kw.sum_max <= prim.sum_max) {
-            free_basis(&c->kw);
+            c->kw = Ks32Basis{};
         }
     }
     if (prim.S == 0) return 0;
-    c->kn = prim;
+    c->kn = std::move(prim);
     // the lazy basis: as many primes below 2^30 as the primary has (the workspaces are sized by S)
     const char* lz = getenv("EXACTO_KS32_LAZY");
     if (!(lz && lz[0] == '0') && wide_mode != 2)
-        if (int e = build_ks32_basis(c, 1ull << 30, qmax, bound, &c->kz, prim.S)) return e;
+        if (int e = build_ks32_basis(c, 1ull << 30, qmax, bound, &c->kz, c->kn.S)) return e;
     use_ks32_basis(c, c->kn);
     return 0;
 }
@@ -817,13 +832,13 @@ static int build_tables(exacto_ctx* c) {
     for (int t = 0; t < NP; ++t)
         pc[t] = make_prime_const(c->primes[t], c->n, c->logn, &tw[(size_t)t * 2 * c->n],
                                  &tw[(size_t)t * 2 * c->n + c->n]);
-    HIP_TRY(dev_alloc((void**)&c->d_tw, tw.size() * sizeof(TwPair)));
+    if (int e_ = c->d_tw.alloc(tw.size() * sizeof(TwPair))) return e_;
     if (int e_ = upload(c, c->d_tw, tw.data(), tw.size() * sizeof(TwPair))) return e_;
     for (int t = 0; t < NP; ++t) {
         pc[t].tw_fwd = c->d_tw + (size_t)t * 2 * c->n;
         pc[t].tw_inv = c->d_tw + (size_t)t * 2 * c->n + c->n;
     }
-    HIP_TRY(dev_alloc((void**)&c->d_primes, NP * sizeof(PrimeConst)));   // (uploaded below, with the CRT folds)
+    if (int e_ = c->d_primes.alloc(NP * sizeof(PrimeConst))) return e_;   // (uploaded below, with the CRT folds)
 
     // ---- CRT tables
     CrtTables& C = c->h_crt;
@@ -960,8 +975,8 @@ static int build_tables(exacto_ctx* c) {
         C.special = C.fast && mn > (1ull << 60) - (1ull << 24);
         C.digit_small = c->gbase <= *std::min_element(qv.begin(), qv.end());
     }
-    HIP_TRY(dev_alloc((void**)&c->d_scal, EXACTO_MAX_L * sizeof(u64)));
-    HIP_TRY(dev_alloc((void**)&c->d_crt, sizeof(CrtTables)));
+    if (int e_ = c->d_scal.alloc(EXACTO_MAX_L * sizeof(u64))) return e_;
+    if (int e_ = c->d_crt.alloc(sizeof(CrtTables))) return e_;
     if (int e_ = upload(c, c->d_crt, &C, sizeof(CrtTables))) return e_;
     return 0;
 }
@@ -1176,38 +1191,24 @@ extern "C" void exacto_ctx_destroy(exacto_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (LaneSet& l : c->xl)
+        if (l.stream) (void)hipStreamSynchronize(l.stream);
     // EXACTO_LEAK_CTX=1 (diagnostic of DESIGN.md §3): keep every allocation of a destroyed context
     static const bool leak = [] { const char* e = getenv("EXACTO_LEAK_CTX"); return e && e[0] == '1'; }();
     if (leak) return;
     for (auto& r : c->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    free_dev(c->d_primes); free_dev(c->d_tw); free_dev(c->d_crt); free_dev(c->d_scal); free_dev(c->d_rlk); free_dev(c->d_rlk_s);
-    free_dev(c->ws_coefQ); free_dev(c->ws_extP); free_dev(c->ws_T); free_dev(c->ws_D); free_dev(c->chain_buf); free_dev(c->chain_coef); free_dev(c->dec_buf); free_dev(c->dig_buf);
     for (LaneSet& l : c->xl) {
-        if (l.stream) { (void)hipStreamSynchronize(l.stream); (void)hipStreamDestroy(l.stream); }
+        if (l.stream) (void)hipStreamDestroy(l.stream);
         if (l.join) (void)hipEventDestroy(l.join);
-        free_dev(l.coefQ); free_dev(l.extP); free_dev(l.T); free_dev(l.D); free_dev(l.DS); free_dev(l.U);
-        if (l.D16) (void)hipFree(l.D16);
     }
-    free_dev(c->ext_a); free_dev(c->ext_b);
-    free_dev((u64*)c->d_cdt); free_dev(c->d_gpow); free_dev(c->d_delta); free_dev(c->enc_buf); free_dev(c->d_lin); free_dev(c->gk_s); free_dev(c->d_gk_rs); free_dev(c->d_dall); free_dev(c->d_hdig); free_dev(c->d_dk); free_dev(c->d_dsk); free_dev(c->d_uk); free_dev(c->pl_buf);
-    if (c->ws_D16) (void)hipFree(c->ws_D16);
-    free_dev(c->d_rs);   // the active basis' tables belong to kn / kz
-    free_dev(c->kn.d_p32); free_dev(c->kn.d_tw32); free_dev(c->kn.d_kst); free_dev(c->kn.d_rs);
-    free_dev(c->kz.d_p32); free_dev(c->kz.d_tw32); free_dev(c->kz.d_kst); free_dev(c->kz.d_rs);
-    free_dev(c->kw.d_p32); free_dev(c->kw.d_tw32); free_dev(c->kw.d_kst); free_dev(c->kw.d_rs);
-    free_dev(c->ws_DS); free_dev(c->ws_U);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     for (int i = 0; i < exacto_ctx::MAX_TWINS; ++i) {
         if (c->twin[i]) exacto_ctx_destroy(c->twin[i]);
         if (c->ev_twin_out[i]) (void)hipEventDestroy(c->ev_twin_out[i]);
     }
     if (c->ev_twin_in) (void)hipEventDestroy(c->ev_twin_in);
-    free_dev(c->io); free_dev(c->prod); free_dev(c->d_off); free_dev(c->d_term_start); free_dev(c->d_terms);
-    free_dev(c->d_slot_start); free_dev(c->gsum_buf); free_dev(c->msw_buf);
-    free_dev(c->d_btw); free_dev(c->d_bperm); free_dev(c->batch_buf);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    free_dev(c->boot_buf); free_dev(c->boot_slots);
-    delete c;
+    delete c;   // every device buffer is a DevBuf member: released here
 }
 
 extern "C" int exacto_ctx_get_info(const exacto_ctx* c, exacto_ctx_info* info) {
@@ -1265,7 +1266,7 @@ extern "C" uint64_t* exacto_ctx_relin_key_buffer(exacto_ctx* c, size_t num_keys)
     if (!c) return nullptr;
     const size_t bytes = num_keys * 2 * c->L * poly_bytes(c);
     if (hipSetDevice(c->device) != hipSuccess) return nullptr;
-    if (grow(&c->d_rlk, &c->rlk_cap, std::max<size_t>(bytes, 8))) return nullptr;
+    if (c->d_rlk.grow(bytes)) return nullptr;
     c->rlk_keys = num_keys;
     c->rlk_loaded = true;
     c->rlk_s_valid = false;  // contents change: companions recomputed before first use
@@ -1402,7 +1403,7 @@ static int run_inv_tensor(exacto_ctx* c, const Operands& o, int cnt, bool p2only
     ProfScope ps(c, PK_TENSOR, (u64)cnt * (p2only ? 3 * c->L + c->K : 3 * NP), bytes);
     // the exact path's scale kernels take T in [0, 2q) (shoup products, 30-bit-limb dot products with
     // headroom); the HPS scale subtracts residues as canonical
-    launch_inv_tensor(o, c->ws_extP, c->ws_T, cnt, c->logn, c->L, c->K, lazy, c->d_primes, c->stream, near60, p2only,
+    launch_inv_tensor(o, c->ws.extP, c->ws.T, cnt, c->logn, c->L, c->K, lazy, c->d_primes, c->stream, near60, p2only,
                       qbits, c->tensor_share_npairs, near60 && c->path != EXACTO_PATH_HPS, fold, square);
     CHECK_LAUNCH();
     return 0;
@@ -1425,26 +1426,24 @@ static NttBatch contiguous(u64* data, long count_items, long poly_per_item, int 
 
 // ============================================================== workspace
 
-static int ensure_workspace(exacto_ctx* c, size_t items) {
-    if (c->ws_items >= items) return 0;
-    free_dev(c->ws_coefQ); free_dev(c->ws_extP); free_dev(c->ws_T); free_dev(c->ws_D);
-    c->ws_coefQ = c->ws_extP = c->ws_T = c->ws_D = nullptr;
-    c->ws_items = 0;
+// The one copy of the workspace sizes.  Every buffer is released before the first is allocated; a
+// failed allocation leaves items at 0, so the next call allocates again.
+int Workspace::ensure(const exacto_ctx* c, size_t want) {
+    if (items >= want) return 0;
+    items = 0;
+    coefQ.reset(); extP.reset(); T.reset(); D.reset(); D16.reset(); DS.reset(); U.reset();
     const size_t pb = poly_bytes(c);
     const int NP = c->L + c->K;
-    HIP_TRY(dev_alloc((void**)&c->ws_coefQ, items * 4 * c->L * pb));
-    HIP_TRY(dev_alloc((void**)&c->ws_extP, items * 4 * std::max(c->K, 1) * pb));
-    HIP_TRY(dev_alloc((void**)&c->ws_T, items * 3 * NP * pb));
-    HIP_TRY(dev_alloc((void**)&c->ws_D, items * std::max(c->G, 1) * c->L * pb));
-    if (c->ws_D16) (void)hipFree(c->ws_D16);
-    HIP_TRY(dev_alloc((void**)&c->ws_D16, items * std::max(c->G, 1) * c->n * sizeof(int16_t)));
-    free_dev(c->ws_DS); free_dev(c->ws_U);
-    c->ws_DS = c->ws_U = nullptr;
-    if (c->S32) {  // ks32: digit residues [item][G][S][n] and accumulators [item][2L][S][n]
-        HIP_TRY(dev_alloc((void**)&c->ws_DS, items * std::max(c->G, 1) * c->S32 * c->n * sizeof(uint32_t)));
-        HIP_TRY(dev_alloc((void**)&c->ws_U, items * 2 * c->L * c->S32 * c->n * sizeof(uint32_t)));
+    if (int e = coefQ.alloc(want * 4 * c->L * pb)) return e;
+    if (int e = extP.alloc(want * 4 * std::max(c->K, 1) * pb)) return e;
+    if (int e = T.alloc(want * 3 * NP * pb)) return e;
+    if (int e = D.alloc(want * std::max(c->G, 1) * c->L * pb)) return e;
+    if (int e = D16.alloc(want * std::max(c->G, 1) * c->n * sizeof(int16_t))) return e;
+    if (c->S32) {
+        if (int e = DS.alloc(want * std::max(c->G, 1) * c->S32 * c->n * sizeof(uint32_t))) return e;
+        if (int e = U.alloc(want * 2 * c->L * c->S32 * c->n * sizeof(uint32_t))) return e;
     }
-    c->ws_items = items;
+    items = want;
     return 0;
 }
 
@@ -1454,26 +1453,7 @@ static int ensure_lane(exacto_ctx* c, int idx, size_t items) {
     LaneSet& l = c->xl[idx - 1];
     if (!l.stream) HIP_TRY(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
     if (!l.join) HIP_TRY(hipEventCreateWithFlags(&l.join, hipEventDisableTiming));
-    if (l.items >= items) return 0;
-    free_dev(l.coefQ); free_dev(l.extP); free_dev(l.T); free_dev(l.D); free_dev(l.DS); free_dev(l.U);
-    if (l.D16) (void)hipFree(l.D16);
-    l.coefQ = l.extP = l.T = l.D = nullptr;
-    l.D16 = nullptr;
-    l.DS = l.U = nullptr;
-    l.items = 0;
-    const size_t pb = poly_bytes(c);
-    const int NP = c->L + c->K;
-    HIP_TRY(dev_alloc((void**)&l.coefQ, items * 4 * c->L * pb));
-    HIP_TRY(dev_alloc((void**)&l.extP, items * 4 * std::max(c->K, 1) * pb));
-    HIP_TRY(dev_alloc((void**)&l.T, items * 3 * NP * pb));
-    HIP_TRY(dev_alloc((void**)&l.D, items * std::max(c->G, 1) * c->L * pb));
-    HIP_TRY(dev_alloc((void**)&l.D16, items * std::max(c->G, 1) * c->n * sizeof(int16_t)));
-    if (c->S32) {
-        HIP_TRY(dev_alloc((void**)&l.DS, items * std::max(c->G, 1) * c->S32 * c->n * sizeof(uint32_t)));
-        HIP_TRY(dev_alloc((void**)&l.U, items * 2 * c->L * c->S32 * c->n * sizeof(uint32_t)));
-    }
-    l.items = items;
-    return 0;
+    return l.ws.ensure(c, items);
 }
 
 // Points the context's stream and workspace at lane idx (> 0) for the lifetime of the guard.
@@ -1481,42 +1461,56 @@ struct LaneGuard {
     exacto_ctx* c;
     int idx;
     LaneGuard(exacto_ctx* c_, int idx_) : c(c_), idx(idx_) { if (idx > 0) flip(); }
+    LaneGuard(const LaneGuard&) = delete;
+    LaneGuard& operator=(const LaneGuard&) = delete;
     ~LaneGuard() { if (idx > 0) flip(); }
     void flip() {
         LaneSet& l = c->xl[idx - 1];
         std::swap(c->stream, l.stream);
-        std::swap(c->ws_coefQ, l.coefQ); std::swap(c->ws_extP, l.extP);
-        std::swap(c->ws_T, l.T); std::swap(c->ws_D, l.D); std::swap(c->ws_D16, l.D16);
-        std::swap(c->ws_DS, l.DS); std::swap(c->ws_U, l.U);
+        std::swap(c->ws, l.ws);
     }
 };
 
-// Lanes for a pass of nchunks chunks of C items: extra lanes forked off c->stream (their
-// streams wait for everything enqueued so far); LaneJoin makes c->stream wait for them again.
-static int fork_lanes(exacto_ctx* c, long nchunks, size_t C, int* nl) {
-    *nl = (c->dual && !c->prof) ? (int)std::min<long>(c->lanes, nchunks) : 1;
-    if (*nl <= 1) return 0;
-    for (int i = 1; i < *nl; ++i)
-        if (int e = ensure_lane(c, i, C)) return e;
-    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-    for (int i = 1; i < *nl; ++i) HIP_TRY(hipStreamWaitEvent(c->xl[i - 1].stream, c->ev_fork, 0));
-    return 0;
-}
-
-struct LaneJoin {
-    exacto_ctx* c;
-    int nl;
-    ~LaneJoin() {
+// One pass of nchunks chunks of C items over the lanes.  begin() sizes lane 0's workspace and forks
+// the extra lanes off c->stream (their streams wait for everything enqueued so far, so whatever
+// their kernels read -- converted keys, per-lane scratch -- is made before it); chunk i runs under
+// chunk(i), on lane i % lanes(); the destructor makes c->stream wait for the extra lanes again, also
+// on an error return from inside the chunk loop (the chunk's guard has flipped back by then).
+// Profiling keeps one lane, so that its per-kernel events time each kernel alone.
+struct LanePass {
+    exacto_ctx* c = nullptr;
+    int nl = 1;
+    LanePass() = default;
+    LanePass(const LanePass&) = delete;
+    LanePass& operator=(const LanePass&) = delete;
+    static int count(const exacto_ctx* c, long nchunks) {
+        return (c->dual && !c->prof) ? (int)std::min<long>(c->lanes, nchunks) : 1;
+    }
+    int begin(exacto_ctx* c_, long nchunks, size_t C) {
+        c = c_;
+        if (int e = c->ws.ensure(c, C)) return e;
+        const int want = count(c, nchunks);
+        if (want <= 1) return 0;
+        for (int i = 1; i < want; ++i)
+            if (int e = ensure_lane(c, i, C)) return e;
+        HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
+        for (int i = 1; i < want; ++i) HIP_TRY(hipStreamWaitEvent(c->xl[i - 1].stream, c->ev_fork, 0));
+        nl = want;   // (a failed fork joins nothing)
+        return 0;
+    }
+    ~LanePass() {
         for (int i = 1; i < nl; ++i)
             if (hipEventRecord(c->xl[i - 1].join, c->xl[i - 1].stream) == hipSuccess)
                 (void)hipStreamWaitEvent(c->stream, c->xl[i - 1].join, 0);
     }
+    int lanes() const { return nl; }
+    LaneGuard chunk(long i) const { return LaneGuard(c, (int)(i % nl)); }
 };
 
 static int ensure_rlk_companions(exacto_ctx* c) {
     if (c->rlk_s_valid) return 0;
     const size_t count = c->rlk_keys * 2 * c->L * (size_t)c->n;
-    if (grow(&c->d_rlk_s, &c->rlk_s_cap, std::max<size_t>(count * sizeof(u64), 8))) return EXACTO_ERR_HIP;
+    if (c->d_rlk_s.grow(count * sizeof(u64))) return EXACTO_ERR_HIP;
     launch_shoup_companions(c->d_rlk, c->d_rlk_s, (long)count, c->n, c->L, c->d_primes, c->stream);
     CHECK_LAUNCH();
     c->rlk_s_valid = true;
@@ -1531,12 +1525,11 @@ static int crt_mode(const exacto_ctx* c) {
 // A key [keys][2][L][n] (NTT domain mod q_l) in ks32's auxiliary basis: INTT mod q_l
 // (coefficient domain), balanced, reduced mod each p_s, forward NTT mod p_s -> dst [keys][2L][S][n]
 // (grown as needed).
-static int ks32_convert_key(exacto_ctx* c, const u64* key, size_t keys, uint32_t** dst, size_t* cap, int S = 0,
+static int ks32_convert_key(exacto_ctx* c, const u64* key, size_t keys, DevBuf<uint32_t>& dst, int S = 0,
                             const Prime32* p32 = nullptr, int form = 0) {
     if (!S) { S = c->S32; p32 = c->d_p32; form = c->ks32_mac_form; }
     const long rows = (long)keys * 2 * c->L;
-    if (grow((u64**)dst, cap, std::max<size_t>((size_t)rows * S * c->n * sizeof(uint32_t), 8)))
-        return EXACTO_ERR_HIP;
+    if (dst.grow((size_t)rows * S * c->n * sizeof(uint32_t))) return EXACTO_ERR_HIP;
     Scratch ks;
     HIP_TRY(ks.alloc((size_t)rows * c->n * sizeof(u64), c->stream, c->pool, c->debug_scratch));
     NttBatch nb{};
@@ -1544,7 +1537,7 @@ static int ks32_convert_key(exacto_ctx* c, const u64* key, size_t keys, uint32_t
     nb.dst = ks.as<u64>(); nb.dst_item_stride = 2L * c->L * c->n;
     nb.ppi = 2 * c->L; nb.prime_base = 0; nb.period = c->L;
     if (int e = run_ntt(c, nb, rows, true)) return e;
-    ks32_key(ks.as<u64>(), *dst, rows, c->L, S, c->logn, p32, c->d_primes, form, c->stream);
+    ks32_key(ks.as<u64>(), dst, rows, c->L, S, c->logn, p32, c->d_primes, form, c->stream);
     CHECK_LAUNCH();
     return 0;
 }
@@ -1609,10 +1602,7 @@ static int ks32_select_basis(exacto_ctx* c) {
 static int ensure_rs(exacto_ctx* c) {
     if (c->rs_valid) return 0;
     if (int e = ks32_select_basis(c)) return e;
-    size_t cap = c->rs_cap;
-    const int e = ks32_convert_key(c, c->d_rlk, c->rlk_keys, &c->d_rs, &cap);
-    c->rs_cap = cap;
-    if (e) return e;
+    if (int e = ks32_convert_key(c, c->d_rlk, c->rlk_keys, c->d_rs)) return e;
     c->rs_valid = true;
     return 0;
 }
@@ -1620,10 +1610,7 @@ static int ensure_rs(exacto_ctx* c) {
 // ... and in the wide basis (dBFV digit sums), on first use after each key load
 static int ensure_rs_wide(exacto_ctx* c) {
     if (c->kw.rs_valid) return 0;
-    size_t cap = c->kw.rs_cap;
-    const int e = ks32_convert_key(c, c->d_rlk, c->rlk_keys, &c->kw.d_rs, &cap, c->kw.S, c->kw.d_p32, c->kw.mac_form);
-    c->kw.rs_cap = cap;
-    if (e) return e;
+    if (int e = ks32_convert_key(c, c->d_rlk, c->rlk_keys, c->kw.d_rs, c->kw.S, c->kw.d_p32, c->kw.mac_form)) return e;
     c->kw.rs_valid = true;
     return 0;
 }
@@ -1659,7 +1646,6 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
         if (ps.on) half = (half + ps.npairs - 1) / ps.npairs * ps.npairs;
         if (half < (size_t)P) C = half;
     }
-    if (int e = ensure_workspace(c, C)) return e;
     // int16 gadget digits (base <= 2^16, exact path): the scale kernel writes each digit once
     const bool d16 = relin && guse > 0 && c->digit16 && c->path != EXACTO_PATH_HPS &&
                      c->gbase <= 65536;
@@ -1677,14 +1663,12 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
         // it uses, which may be the wide one: the primary form would be built and never read)
         if (int e = k32 ? (c->ks_defer ? 0 : ensure_rs(c)) : ensure_rlk_companions(c)) return e;
     }
-    // two chunks or more: odd chunks on the second lane (profiling keeps one lane so its per-kernel
-    // events time each kernel alone)
-    int nl = 1;
-    if (int e = fork_lanes(c, (P + (long)C - 1) / (long)C, C, &nl)) return e;
-    LaneJoin join{c, nl};
+    // two chunks or more: odd chunks on the second lane
+    LanePass pass;
+    if (int e = pass.begin(c, (P + (long)C - 1) / (long)C, C)) return e;
     for (long s = 0; s < P; s += (long)C) {
         const int cnt = (int)std::min<long>((long)C, P - s);
-        LaneGuard lane(c, (int)((s / (long)C) % nl));
+        LaneGuard lane = pass.chunk(s / (long)C);
         Operands o = op;
         if (o.a_off) o.a_off += s; else o.a += s * o.a_stride;
         if (square) { o.b = nullptr; o.b_off = nullptr; }
@@ -1695,28 +1679,28 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
             const long ip = square ? 2 : 4;   // input polynomials per product
             NttBatch nb{};
             nb.src = o.a; nb.src_off = o.a_off; nb.src_item_stride = o.a_stride;
-            nb.dst = c->ws_coefQ; nb.dst_item_stride = ip * Ln;
+            nb.dst = c->ws.coefQ; nb.dst_item_stride = ip * Ln;
             nb.ppi = 2 * L; nb.prime_base = 0; nb.period = L;
             if (int e = run_ntt(c, nb, (long)cnt * 2 * L, true)) return e;
             if (!square) {
                 nb.src = o.b; nb.src_off = o.b_off; nb.src_item_stride = o.b_stride;
-                nb.dst = c->ws_coefQ + 2 * Ln;
+                nb.dst = c->ws.coefQ + 2 * Ln;
                 if (int e = run_ntt(c, nb, (long)cnt * 2 * L, true)) return e;
             }
             // 2. extension to the auxiliary primes
             if (c->path == EXACTO_PATH_HPS) {
                 // per input poly: the q residues in, K auxiliary residues out
                 ProfScope pl(c, PK_HPS_EXT, (u64)ip * cnt, 8.0 * (1 + K) * n * (double)ip * cnt);
-                launch_hps_extend(c->ws_coefQ, c->ws_extP, ip * cnt, n, c->d_primes, K, c->stream);
+                launch_hps_extend(c->ws.coefQ, c->ws.extP, ip * cnt, n, c->d_primes, K, c->stream);
             } else {
                 ProfScope pl(c, PK_LIFT, (u64)ip * cnt, 8.0 * (L + K) * n * (double)ip * cnt);
-                launch_exact_lift(c->ws_coefQ, c->ws_extP, ip * cnt, n, c->d_crt, c->d_primes, L, K,
+                launch_exact_lift(c->ws.coefQ, c->ws.extP, ip * cnt, n, c->d_crt, c->d_primes, L, K,
                                   crt_mode(c), c->stream);
             }
             CHECK_LAUNCH();
             // 3. forward NTT of the extended polynomials (exact path with the asm tensor, its only
             // reader: outputs left in [0, 2q), which its products take)
-            NttBatch eb = contiguous(c->ws_extP, cnt, ip * K, L, K, n);
+            NttBatch eb = contiguous(c->ws.extP, cnt, ip * K, L, K, n);
             eb.lazy_out = c->path != EXACTO_PATH_HPS && tensor_asm(c);
             if (int e = run_ntt(c, eb, (long)cnt * ip * K, false)) return e;
         } else {
@@ -1733,18 +1717,18 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
             const int ib_cnt = cnt / ps.npairs;
             {   // per (item, prime): the 2d input ciphertexts' two polys in, 2 sums per output limb out
                 ProfScope pp(c, PK_PAIRSUM, (u64)ib_cnt * K * ps.d, 8.0 * n * K * ib_cnt * (4.0 * ps.d + 2.0 * ps.d));
-                launch_dbfv_pairsum(o, c->ws_extP, ib_cnt, ps.d, ps.npairs, ps.term_start, ps.terms, L, K, n,
+                launch_dbfv_pairsum(o, c->ws.extP, ib_cnt, ps.d, ps.npairs, ps.term_start, ps.terms, L, K, n,
                                     c->d_primes, c->stream);
             }
             CHECK_LAUNCH();
-            if (int e = run_ntt(c, contiguous(c->ws_extP, (long)ib_cnt * ps.d, 2L * K, L, K, n),
+            if (int e = run_ntt(c, contiguous(c->ws.extP, (long)ib_cnt * ps.d, 2L * K, L, K, n),
                                 (long)ib_cnt * ps.d * 2 * K, true))
                 return e;
         }
         // 6. scale-and-round (+ gadget digits of the third component)
         u64* R = out + s * out_stride;
         const int ncomp = relin ? 2 : 3;
-        u64* D = relin ? c->ws_D : nullptr;
+        u64* D = relin ? c->ws.D : nullptr;
         // scale bytes per item: the three components' L+K residues in; c0, c1 (L residues each) out
         // (psum: c2 only), and the third component's digits (int16 / int8) or its L residues
         const double dig_b = (d16 || hps_defer) ? (c->ks_defer && c->ks_defer8 ? 1.0 : 2.0) * guse
@@ -1756,15 +1740,15 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
             void* d16p = hps_defer ? (c->ks_defer8 ? (void*)((int8_t*)c->ks_defer + s * (long)guse * n)
                                                    : (void*)(c->ks_defer + s * (long)guse * n))
                                    : nullptr;
-            launch_hps_scale(c->ws_T, R, out_stride, ncomp, hps_defer ? nullptr : D, d16p,
+            launch_hps_scale(c->ws.T, R, out_stride, ncomp, hps_defer ? nullptr : D, d16p,
                              hps_defer && c->ks_defer8, guse, cnt, n, c->d_crt, c->d_primes, K, c->hps_fast,
                              c->stream);
         } else
-            launch_exact_scale(c->ws_T, R, out_stride, ncomp, d16 ? nullptr : D,
+            launch_exact_scale(c->ws.T, R, out_stride, ncomp, d16 ? nullptr : D,
                                d16 ? (c->ks_defer ? (c->ks_defer8
                                                          ? (int16_t*)((int8_t*)c->ks_defer + s * (long)guse * n)
                                                          : c->ks_defer + s * (long)guse * n)
-                                                  : c->ws_D16)
+                                                  : c->ws.D16)
                                    : nullptr,
                                guse, cnt, n, c->d_crt, c->d_primes, L, K, crt_mode(c),
                                c->stream, c->h_crt.gshift, ps.on, c->ks_defer && c->ks_defer8, c->fp_crt, c->fpq_lim,
@@ -1778,7 +1762,7 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
             // residues (L each) in, the limb's L residues out, for c0 and c1
             ProfScope pq(c, PK_PSUM_SCALE, (u64)(cnt / ps.npairs) * ps.d,
                          ib * 2.0 * n * 8.0 * (ps.d * (double)(K + L) + (double)ps.npairs * L));
-            if (!launch_psum_scale(c->ws_T, c->ws_extP, ps.out + item0 * ps.d * 2 * Ln, cnt / ps.npairs, ps.d, ps.npairs,
+            if (!launch_psum_scale(c->ws.T, c->ws.extP, ps.out + item0 * ps.d * 2 * Ln, cnt / ps.npairs, ps.d, ps.npairs,
                                    ps.term_start, ps.terms, n, c->d_crt, c->d_primes, L, c->stream, ps.fpc,
                                    c->fpq_lim))
                 return fail(EXACTO_ERR_HIP, "internal: psum scale not available for these limbs");
@@ -1796,15 +1780,15 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
             if (!c->ks_defer) {   // (deferred: the caller sums the digits of products first, dbfv_mul_core)
                 {   // int16 digit in (2 B), 31-bit residue out (4 B) per coefficient and prime
                     ProfScope pd(c, PK_KS_DIGITS, (u64)cnt * guse * c->S32, 6.0 * n * cnt * guse * c->S32);
-                    ks32_digits(c->ws_D16, c->ws_DS, cnt, guse, c->S32, c->logn, c->d_p32, c->ks32_mac_form, c->stream);
+                    ks32_digits(c->ws.D16, c->ws.DS, cnt, guse, c->S32, c->logn, c->d_p32, c->ks32_mac_form, c->stream);
                 }
                 {   // per (item, prime, coefficient): G digit residues in, 2L sums out (the key slice from LDS)
                     ProfScope pm(c, PK_KS_MAC, (u64)cnt * c->S32, 4.0 * n * cnt * c->S32 * (guse + 2.0 * L));
-                    ks32_mac(c->ws_DS, c->d_rs, c->ws_U, cnt, guse, L, c->S32, n, c->d_p32, c->ks32_mac_form, c->stream);
+                    ks32_mac(c->ws.DS, c->d_rs, c->ws.U, cnt, guse, L, c->S32, n, c->d_p32, c->ks32_mac_form, c->stream);
                 }
                 {   // per (item, component, limb): S 31-bit sums in, R in and out
                     ProfScope pc(c, PK_KS_CRT, (u64)cnt * 2 * L, (double)n * cnt * 2 * L * (4.0 * c->S32 + 16.0));
-                    ks32_crt(c->ws_U, R, out_stride, cnt, L, c->S32, c->logn, c->d_kst, c->d_p32, c->d_primes, c->ks32_mac_form,
+                    ks32_crt(c->ws.U, R, out_stride, cnt, L, c->S32, c->logn, c->d_kst, c->d_p32, c->d_primes, c->ks32_mac_form,
                              c->stream, c->ks_fpc && c->ks32_fpc_max >= 1);
                 }
                 CHECK_LAUNCH();
@@ -1813,9 +1797,9 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
         if (skip_fwd) continue;   // (hps_defer: digits and c0 / c1 are the caller's now)
         if (int e = run_ntt(c, rb, (long)cnt * ncomp * L, false)) return e;
         if (relin && guse > 0 && !k32) {
-            NttBatch db = contiguous(c->ws_D, cnt, (long)guse * L, 0, L, n);
+            NttBatch db = contiguous(c->ws.D, cnt, (long)guse * L, 0, L, n);
             if (d16) {  // int16 digits [item][g][n] -> NTT residues [item][g][L][n]
-                db.src16 = c->ws_D16;
+                db.src16 = c->ws.D16;
                 db.src16_item_stride = (long)guse * n;
             }
             if (int e = run_ntt(c, db, (long)cnt * guse * L, false)) return e;
@@ -1823,7 +1807,7 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
             if (int e = ensure_rlk_companions(c)) return e;
             {   // per item: c0, c1 and the G digit residues in, c0, c1 out (the key from LDS)
                 ProfScope pm(c, PK_RELIN_MAC, (u64)cnt, 8.0 * n * L * cnt * (4.0 + guse));
-                launch_relin_mac(R, out_stride, c->ws_D, c->d_rlk, c->d_rlk_s, guse, R, out_stride, cnt, n, L,
+                launch_relin_mac(R, out_stride, c->ws.D, c->d_rlk, c->d_rlk_s, guse, R, out_stride, cnt, n, L,
                                  c->d_primes, c->stream);
             }
             CHECK_LAUNCH();
@@ -1863,14 +1847,14 @@ extern "C" int exacto_rns_inv_dev(exacto_ctx* c, uint64_t* p, size_t count) {
 }
 
 static int stage(exacto_ctx* c, size_t bytes) {
-    if (grow(&c->io, &c->io_bytes, bytes)) return EXACTO_ERR_HIP;
+    if (c->io.grow(bytes)) return EXACTO_ERR_HIP;
     return 0;
 }
 
 static int ntt_host(exacto_ctx* c, uint64_t* polys, size_t count, size_t limb, bool inverse) {
     if (int e = check_ctx(c)) return e;
     const size_t bytes = count * poly_bytes(c);
-    if (int e = stage(c, std::max<size_t>(bytes, 8))) return e;
+    if (int e = stage(c, bytes)) return e;
     if (int e_ = upload(c, c->io, polys, bytes)) return e_;
     if (int e = ntt_dev(c, c->io, count, limb, inverse)) return e;
     HIP_TRY(hipMemcpyAsync(polys, c->io, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2053,7 +2037,7 @@ extern "C" int exacto_relinearize_dev(exacto_ctx* c, const uint64_t* ct, size_t 
     if (!c->rlk_loaded) return fail(EXACTO_ERR_MISSING_KEY, "key not available: relinearization key not loaded");
     const int guse = (int)std::min<size_t>(c->G, c->rlk_keys);
     const size_t C = std::min<size_t>(c->chunk, std::max<size_t>(B, 1));
-    if (int e = ensure_workspace(c, C)) return e;
+    if (int e = c->ws.ensure(c, C)) return e;
     for (size_t s = 0; s < B; s += C) {
         const int cnt = (int)std::min(C, B - s);
         const u64* src = ct + s * 3 * Ln;
@@ -2064,21 +2048,21 @@ extern "C" int exacto_relinearize_dev(exacto_ctx* c, const uint64_t* ct, size_t 
         if (guse == 0) continue;
         NttBatch nb{};
         nb.src = src + 2 * Ln; nb.src_off = nullptr; nb.src_item_stride = 3 * Ln;
-        nb.dst = c->ws_coefQ; nb.dst_item_stride = Ln;
+        nb.dst = c->ws.coefQ; nb.dst_item_stride = Ln;
         nb.ppi = c->L; nb.prime_base = 0; nb.period = c->L;
         if (int e = run_ntt(c, nb, (long)cnt * c->L, true)) return e;
         const bool d16 = c->digit16 && c->gbase <= 65536;  // int16 digits, as in run_mul
-        launch_decompose(c->ws_coefQ, Ln, c->ws_D, guse, cnt, c->n, c->d_crt, c->d_primes, c->L, c->stream,
-                         d16 ? c->ws_D16 : nullptr);
+        launch_decompose(c->ws.coefQ, Ln, c->ws.D, guse, cnt, c->n, c->d_crt, c->d_primes, c->L, c->stream,
+                         d16 ? c->ws.D16 : nullptr);
         CHECK_LAUNCH();
-        NttBatch db = contiguous(c->ws_D, cnt, (long)guse * c->L, 0, c->L, c->n);
+        NttBatch db = contiguous(c->ws.D, cnt, (long)guse * c->L, 0, c->L, c->n);
         if (d16) {
-            db.src16 = c->ws_D16;
+            db.src16 = c->ws.D16;
             db.src16_item_stride = (long)guse * c->n;
         }
         if (int e = run_ntt(c, db, (long)cnt * guse * c->L, false)) return e;
         if (int e = ensure_rlk_companions(c)) return e;
-        launch_relin_mac(dst, 2 * Ln, c->ws_D, c->d_rlk, c->d_rlk_s, guse, dst, 2 * Ln, cnt, c->n, c->L,
+        launch_relin_mac(dst, 2 * Ln, c->ws.D, c->d_rlk, c->d_rlk_s, guse, dst, 2 * Ln, cnt, c->n, c->L,
                          c->d_primes, c->stream);
         CHECK_LAUNCH();
     }
@@ -2100,9 +2084,9 @@ static int host_call(exacto_ctx* c, const std::vector<std::pair<const void*, siz
     if (int e = check_ctx(c)) return e;
     size_t total = out_bytes;
     for (auto& in : ins) total += (in.second + 255) / 256 * 256;
-    if (int e = stage(c, std::max<size_t>(total, 8))) return e;
+    if (int e = stage(c, total)) return e;
     std::vector<u64*> dins;
-    char* p = (char*)c->io;
+    char* p = (char*)c->io.get();
     for (auto& in : ins) {
         // stream-ordered on the context stream (see upload)
         if (in.second) HIP_TRY(hipMemcpyAsync(p, in.first, in.second, hipMemcpyHostToDevice, c->stream));
@@ -2232,17 +2216,13 @@ static int plan_upload(exacto_ctx* c, size_t B, size_t na, size_t nb, const std:
             off[2 * BP + b * npairs + pi] = (u64)((b * na + pairs[pi].first) * Kn2);
             off[3 * BP + b * npairs + pi] = (u64)((b * nb + pairs[pi].second) * Kn2);
         }
-    size_t cap = c->off_cap;
-    if (grow(&c->d_off, &cap, off.size() * sizeof(u64) + 8)) return EXACTO_ERR_HIP;
-    c->off_cap = cap;
+    if (c->d_off.grow(off.size() * sizeof(u64) + 8)) return EXACTO_ERR_HIP;
     if (int e_ = upload(c, c->d_off, off.data(), off.size() * sizeof(u64))) return e_;
-    free_dev(c->d_term_start);
-    free_dev(c->d_terms);
-    c->d_term_start = nullptr;
-    c->d_terms = nullptr;
-    HIP_TRY(dev_alloc((void**)&c->d_term_start, start.size() * sizeof(int)));
+    c->d_term_start.reset();
+    c->d_terms.reset();
+    if (int e_ = c->d_term_start.alloc(start.size() * sizeof(int))) return e_;
     if (int e_ = upload(c, c->d_term_start, start.data(), start.size() * sizeof(int))) return e_;
-    HIP_TRY(dev_alloc((void**)&c->d_terms, std::max<size_t>(terms.size(), 1) * sizeof(CombineTerm)));
+    if (int e_ = c->d_terms.alloc(std::max<size_t>(terms.size(), 1) * sizeof(CombineTerm))) return e_;
     if (!terms.empty())
         if (int e_ = upload(c, c->d_terms, terms.data(), terms.size() * sizeof(CombineTerm))) return e_;
     c->cached_B = B;
@@ -2350,9 +2330,7 @@ static int mul_sum_plan(exacto_ctx* c, size_t B, size_t na, size_t nb, const uin
     if (int e = plan_upload(c, B, na, nb, pairs, start, terms)) return e;
     const size_t ngroups = start.size() - 1;
     if (ngroups > nslots) {
-        free_dev(c->d_slot_start);
-        c->d_slot_start = nullptr;
-        HIP_TRY(dev_alloc((void**)&c->d_slot_start, slot_start.size() * sizeof(int)));
+        if (int e_ = c->d_slot_start.alloc(slot_start.size() * sizeof(int))) return e_;
         if (int e_ = upload(c, c->d_slot_start, slot_start.data(), slot_start.size() * sizeof(int))) return e_;
     }
     c->cached_kind = 1;
@@ -2408,15 +2386,15 @@ extern "C" int exacto_dbfv_mul_plan(size_t d, uint64_t base, uint64_t plain, int
 static int extend_cts(exacto_ctx* c, const u64* cts, size_t ncts, u64* ext, const u64* coef = nullptr) {
     const int n = c->n, L = c->L, K = c->K;
     const long Ln2 = 2L * L * n, Kn2 = 2L * K * n;
-    if (int e = ensure_workspace(c, std::min<size_t>(c->chunk, (ncts + 1) / 2))) return e;
-    const size_t G = coef ? ncts : 2 * c->ws_items;  // ciphertexts per pass: coefQ holds 4 polys x L per item
+    if (int e = c->ws.ensure(c, std::min<size_t>(c->chunk, (ncts + 1) / 2))) return e;
+    const size_t G = coef ? ncts : 2 * c->ws.items;  // ciphertexts per pass: coefQ holds 4 polys x L per item
     for (size_t g0 = 0; g0 < ncts; g0 += G) {
         const long cnt = (long)std::min(G, ncts - g0);
-        const u64* cq = coef ? coef + g0 * Ln2 : c->ws_coefQ;
+        const u64* cq = coef ? coef + g0 * Ln2 : c->ws.coefQ;
         if (!coef) {
             NttBatch nb{};
             nb.src = cts + g0 * Ln2; nb.src_off = nullptr; nb.src_item_stride = Ln2;
-            nb.dst = c->ws_coefQ; nb.dst_item_stride = Ln2;
+            nb.dst = c->ws.coefQ; nb.dst_item_stride = Ln2;
             nb.ppi = 2 * L; nb.prime_base = 0; nb.period = L;
             if (int e = run_ntt(c, nb, cnt * 2 * L, true)) return e;
         }
@@ -2449,9 +2427,7 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
     const bool grouped = nslots < dout;
     const long Ln2 = 2L * c->L * c->n;
     const long P = (long)B * npairs;
-    size_t cap = c->prod_bytes;
-    if (grow(&c->prod, &cap, (size_t)P * Ln2 * sizeof(u64))) return EXACTO_ERR_HIP;
-    c->prod_bytes = cap;
+    if (c->prod.grow((size_t)P * Ln2 * sizeof(u64))) return EXACTO_ERR_HIP;
     Operands op{};
     const size_t BP = (size_t)B * npairs;
     op.a = a; op.a_off = c->d_off; op.a_stride = 0;
@@ -2459,14 +2435,14 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
     if (c->share_ext && c->K > 0 && !c->deferred_code) {
         const size_t bytes_a = B * na * 2 * c->K * poly_bytes(c), bytes_b = B * nb * 2 * c->K * poly_bytes(c);
         if (c->ext_a_ready) {   // made by the previous chain step (same ciphertexts, same buffer size)
-            if (c->ext_a_cap < bytes_a) return fail(EXACTO_ERR_HIP, "internal: pre-extended operand buffer too small");
+            if (c->ext_a.bytes() < bytes_a) return fail(EXACTO_ERR_HIP, "internal: pre-extended operand buffer too small");
         } else {
-            if (grow(&c->ext_a, &c->ext_a_cap, bytes_a)) return EXACTO_ERR_HIP;
+            if (c->ext_a.grow(bytes_a)) return EXACTO_ERR_HIP;
             if (int e = extend_cts(c, a, B * na, c->ext_a, c->coef_in)) return e;
         }
         c->ext_a_ready = false;
         if (!b_extended && !same_ab) {
-            if (grow(&c->ext_b, &c->ext_b_cap, bytes_b)) return EXACTO_ERR_HIP;
+            if (c->ext_b.grow(bytes_b)) return EXACTO_ERR_HIP;
             if (int e = extend_cts(c, b, B * nb, c->ext_b)) return e;
         }
         op.ea = c->ext_a; op.ea_off = c->d_off + 2 * BP;
@@ -2514,22 +2490,19 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
     if (grouped) {
         // (the HPS sum multiplies with the key after the forward transform, once per output: never grouped)
         if (hps_sum) return fail(EXACTO_ERR_HIP, "internal: grouped product sums on the HPS digit-sum path");
-        if (grow(&c->gsum_buf, &c->gsum_cap, B * dout * (size_t)Ln2 * sizeof(u64))) return EXACTO_ERR_HIP;
+        if (c->gsum_buf.grow(B * dout * (size_t)Ln2 * sizeof(u64))) return EXACTO_ERR_HIP;
     }
     if (hps_sum) {
-        if (grow((u64**)&c->d_dall, &c->dall_cap, std::max<size_t>((size_t)P * gu * c->n * sizeof(int16_t), 8)) ||
-            grow((u64**)&c->d_dk, &c->dk_cap, std::max<size_t>(Bd * gu * c->n * 2, 8)) ||
-            grow(&c->d_hdig, &c->hdig_cap, std::max<size_t>(Bd * gu * c->L * c->n * sizeof(u64), 8)))
+        if (c->d_dall.grow((size_t)P * gu * c->n * sizeof(int16_t)) || c->d_dk.grow(Bd * gu * c->n * 2) ||
+            c->d_hdig.grow(Bd * gu * c->L * c->n * sizeof(u64)))
             return EXACTO_ERR_HIP;
         if (int e = ensure_rlk_companions(c)) return e;
         c->ks_defer = c->d_dall;
         c->ks_defer8 = c->digit8_env && c->gbase <= 256;
     }
     if (sum_ks) {
-        if (grow((u64**)&c->d_dall, &c->dall_cap, std::max<size_t>((size_t)P * gu * c->n * sizeof(int16_t), 8)) ||
-            grow((u64**)&c->d_dk, &c->dk_cap, std::max<size_t>(Bd * gu * c->n * (wide ? 4 : 2), 8)) ||
-            grow((u64**)&c->d_dsk, &c->dsk_cap, std::max<size_t>(Bd * gu * Sn * sizeof(uint32_t), 8)) ||
-            grow((u64**)&c->d_uk, &c->uk_cap, std::max<size_t>(Bd * 2 * c->L * Sn * sizeof(uint32_t), 8)))
+        if (c->d_dall.grow((size_t)P * gu * c->n * sizeof(int16_t)) || c->d_dk.grow(Bd * gu * c->n * (wide ? 4 : 2)) ||
+            c->d_dsk.grow(Bd * gu * Sn * sizeof(uint32_t)) || c->d_uk.grow(Bd * 2 * c->L * Sn * sizeof(uint32_t)))
             return EXACTO_ERR_HIP;
         if (int e = use_wide ? ensure_rs_wide(c) : ensure_rs(c)) return e;
         c->ks_defer = c->d_dall;
@@ -2553,9 +2526,7 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
     // only here, where psum is known to be on (HPS or non-psum chains never allocate it).
     c->coef_out = nullptr;
     if (psum && c->coef_slot >= 0) {
-        size_t ccap = c->chain_coef_bytes;
-        if (grow(&c->chain_coef, &ccap, 2 * c->coef_slot_words * sizeof(u64))) return EXACTO_ERR_HIP;
-        c->chain_coef_bytes = ccap;
+        if (c->chain_coef.grow(2 * c->coef_slot_words * sizeof(u64))) return EXACTO_ERR_HIP;
         c->coef_out = c->chain_coef + (size_t)c->coef_slot * c->coef_slot_words;
     }
     const bool chain_cf = psum && c->coef_out;
@@ -2599,8 +2570,8 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
         }
         {
             ProfScope pn(c, PK_KS_DIGITS, (u64)Bd * gu * S, nn * Bd * gu * S * (ds + 4.0));
-            if (wide) ks32_digits32((const int32_t*)c->d_dk, c->d_dsk, (int)Bd, (int)gu, S, c->logn, p32, mac_form, c->stream);
-            else ks32_digits((const int16_t*)c->d_dk, c->d_dsk, (int)Bd, (int)gu, S, c->logn, p32, mac_form, c->stream);
+            if (wide) ks32_digits32((const int32_t*)c->d_dk.get(), c->d_dsk, (int)Bd, (int)gu, S, c->logn, p32, mac_form, c->stream);
+            else ks32_digits((const int16_t*)c->d_dk.get(), c->d_dsk, (int)Bd, (int)gu, S, c->logn, p32, mac_form, c->stream);
         }
         {
             ProfScope pm(c, PK_KS_MAC, (u64)Bd * S, 4.0 * nn * Bd * S * (gu + 2.0 * c->L));
@@ -2624,7 +2595,7 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
         }
         CHECK_LAUNCH();
         NttBatch db = contiguous(c->d_hdig, (long)Bd, (long)gu * c->L, 0, c->L, c->n);
-        db.src16 = (const int16_t*)c->d_dk;
+        db.src16 = (const int16_t*)c->d_dk.get();
         db.src16_item_stride = (long)gu * c->n;
         if (int e = run_ntt(c, db, (long)Bd * gu * c->L, false)) return e;
     }
@@ -2645,7 +2616,7 @@ static int mul_group_run(exacto_ctx* c, size_t na, size_t nb, const uint64_t* a,
         // launch (cfg5: 512 + 640 polynomials instead of two launches that each fill about one
         // generation of the 512 resident workgroups)
         const bool pre = chain_cf && op.ea != nullptr && dout == na && na == nb && !c->deferred_code &&
-                         c->path != EXACTO_PATH_HPS && c->ext_a_cap >= (size_t)B * na * 2 * c->K * poly_bytes(c);
+                         c->path != EXACTO_PATH_HPS && c->ext_a.bytes() >= (size_t)B * na * 2 * c->K * poly_bytes(c);
         if (pre) {
             const long cts = (long)B * na;
             {
@@ -2971,9 +2942,7 @@ static int decrypt_batch(exacto_ctx* c, const u64* ct, size_t polys, long ct_str
     if (L >= 2 && (c->K < 1 || c->plain >= c->primes[L]))
         return fail(EXACTO_ERR_NOT_IMPLEMENTED, "not yet implemented: GPU decryption needs plain_modulus below the "
                                                 "first internal auxiliary prime");
-    size_t cap = c->dec_bytes;
-    if (grow(&c->dec_buf, &cap, B * L * poly_bytes(c))) return EXACTO_ERR_HIP;
-    c->dec_bytes = cap;
+    if (c->dec_buf.grow(B * L * poly_bytes(c))) return EXACTO_ERR_HIP;
     launch_phase(ct, (int)polys, ct_stride, sk, c->dec_buf, (int)B, n, L, c->d_primes, c->stream);
     CHECK_LAUNCH();
     if (int e = run_ntt(c, contiguous(c->dec_buf, (long)B, L, 0, L, n), (long)B * L, true)) return e;
@@ -3005,9 +2974,7 @@ static int dbfv_decrypt_common(exacto_ctx* c, size_t d, uint64_t base, uint64_t 
         return invalid_param("polynomial dBFV decrypt requires finite plain_modulus (plain_modulus=0 is scalar-only)");
     if (B == 0) return 0;
     const size_t nd = B * d;
-    size_t cap = c->dig_bytes;
-    if (grow(&c->dig_buf, &cap, nd * poly_bytes(c))) return EXACTO_ERR_HIP;
-    c->dig_bytes = cap;
+    if (c->dig_buf.grow(nd * poly_bytes(c))) return EXACTO_ERR_HIP;
     if (int e = decrypt_batch(c, ct, 2, 2L * c->L * c->n, sk, c->dig_buf, nd)) return e;
     launch_dbfv_recompose(c->dig_buf, out, (int)B, c->n, (int)d, base, plain, c->plain, scalar, c->stream);
     CHECK_LAUNCH();
@@ -3104,7 +3071,7 @@ extern "C" int exacto_bfv_mod_switch_dev(exacto_ctx* c, const uint64_t* ct, size
     if (lin - lout == 1) return run_drop_prime(c, ct, out, B * polys, (int)lin, round);
     // several drops: chunk by chunk through two halves of the workspace, the last drop into out
     const size_t C = std::min(c->chunk, B), half = C * polys * (lin - 1) * n;
-    if (grow(&c->msw_buf, &c->msw_cap, 2 * half * sizeof(u64))) return EXACTO_ERR_HIP;
+    if (c->msw_buf.grow(2 * half * sizeof(u64))) return EXACTO_ERR_HIP;
     for (size_t i0 = 0; i0 < B; i0 += C) {
         const size_t cnt = std::min(C, B - i0);
         const u64* src = ct + i0 * iw;
@@ -3150,9 +3117,7 @@ static int noise_batch(exacto_ctx* c, const u64* ct, size_t polys, long ct_strid
                                                 "first internal auxiliary prime");
     if (int e = delta_residues(c)) return e;
     const size_t phase_words = items * L * (size_t)n;
-    size_t cap = c->dec_bytes;
-    if (grow(&c->dec_buf, &cap, (phase_words + items * noise_chunks(n) * L) * sizeof(u64))) return EXACTO_ERR_HIP;
-    c->dec_bytes = cap;
+    if (c->dec_buf.grow((phase_words + items * noise_chunks(n) * L) * sizeof(u64))) return EXACTO_ERR_HIP;
     launch_phase(ct, (int)polys, ct_stride, sk, c->dec_buf, (int)items, n, L, c->d_primes, c->stream);
     CHECK_LAUNCH();
     if (int e = run_ntt(c, contiguous(c->dec_buf, (long)items, L, 0, L, n), (long)items * L, true)) return e;
@@ -3255,9 +3220,7 @@ static int dbfv_chain_one(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain
         return 0;
     }
     if (depth > 1 && B) {
-        size_t cap = c->chain_bytes;
-        if (grow(&c->chain_buf, &cap, 2 * bytes)) return EXACTO_ERR_HIP;
-        c->chain_bytes = cap;
+        if (c->chain_buf.grow(2 * bytes)) return EXACTO_ERR_HIP;
     }
     if (int e = dbfv_params_check(d, base, plain)) return e;
     if (B == 0) return 0;
@@ -3332,9 +3295,7 @@ static int gaussian_table(exacto_ctx* c, double sigma, int* tail, int* len, doub
         cdf.push_back(cum);
     }
     if (c->cdt_sigma != sigma || !c->d_cdt) {
-        size_t cap = c->cdt_cap;
-        if (grow((u64**)&c->d_cdt, &cap, cdf.size() * sizeof(double))) return EXACTO_ERR_HIP;
-        c->cdt_cap = cap;
+        if (c->d_cdt.grow(cdf.size() * sizeof(double))) return EXACTO_ERR_HIP;
         HIP_TRY(hipStreamSynchronize(c->stream));  // in-flight samplers may still read the old table
         if (int e_ = upload(c, c->d_cdt, cdf.data(), cdf.size() * sizeof(double))) return e_;
         c->cdt_sigma = sigma;
@@ -3418,9 +3379,7 @@ extern "C" int exacto_gen_relin_key_dev(exacto_ctx* c, const uint64_t* sk, doubl
             g = (u64)((u128)g * b % q);
         }
     }
-    size_t cap = c->gpow_cap;
-    if (grow(&c->d_gpow, &cap, gpow.size() * sizeof(u64))) return EXACTO_ERR_HIP;
-    c->gpow_cap = cap;
+    if (c->d_gpow.grow(gpow.size() * sizeof(u64))) return EXACTO_ERR_HIP;
     // the table is host-pageable and d_gpow may still be read by a previous call's kernels
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int e_ = upload(c, c->d_gpow, gpow.data(), gpow.size() * sizeof(u64))) return e_;
@@ -3475,7 +3434,8 @@ static int delta_residues(exacto_ctx* c) {
         dr[i] = (u64)r;
         dr[EXACTO_MAX_L + i] = shoup_h((u64)r, c->primes[i]);
     }
-    if (!c->d_delta) HIP_TRY(dev_alloc((void**)&c->d_delta, 2 * EXACTO_MAX_L * sizeof(u64)));
+    if (!c->d_delta)
+        if (int e_ = c->d_delta.alloc(2 * EXACTO_MAX_L * sizeof(u64))) return e_;
     if (int e_ = upload(c, c->d_delta, dr.data(), dr.size() * sizeof(u64))) return e_;
     c->delta_ok = true;
     return 0;
@@ -3506,9 +3466,7 @@ static int encrypt_batch(exacto_ctx* c, const u64* pt, const u64* sk, const u64*
     const long Ln = (long)c->L * c->n;
     const ChaChaKey k = chacha_key(key);
     // scratch: Delta m [items][L][n], and u [items][L][n] for pk-encryption
-    size_t cap = c->enc_cap;
-    if (grow(&c->enc_buf, &cap, items * (pk ? 2 : 1) * Ln * sizeof(u64))) return EXACTO_ERR_HIP;
-    c->enc_cap = cap;
+    if (c->enc_buf.grow(items * (pk ? 2 : 1) * Ln * sizeof(u64))) return EXACTO_ERR_HIP;
     u64* dm = c->enc_buf;
     u64* u = c->enc_buf + items * Ln;
     if (dp)
@@ -3565,9 +3523,7 @@ extern "C" int exacto_gen_galois_key_dev(exacto_ctx* c, const uint64_t* sk, uint
     if (num_keys == 0) return 0;
     const int n = c->n, L = c->L;
     const long Ln = (long)L * n;
-    size_t cap = c->enc_cap;
-    if (grow(&c->enc_buf, &cap, (size_t)(2 * n + Ln) * sizeof(u64))) return EXACTO_ERR_HIP;
-    c->enc_cap = cap;
+    if (c->enc_buf.grow((size_t)(2 * n + Ln) * sizeof(u64))) return EXACTO_ERR_HIP;
     u64 *t0 = c->enc_buf, *t1 = t0 + n, *s_auto = t1 + n;
     HIP_TRY(dev_copy(t0, sk, n * sizeof(u64), c->stream));
     if (int e = run_ntt(c, contiguous(t0, 1, 1, 0, 1, n), 1, true)) return e;
@@ -3585,9 +3541,7 @@ extern "C" int exacto_gen_galois_key_dev(exacto_ctx* c, const uint64_t* sk, uint
             g = (u64)((u128)g * b % q);
         }
     }
-    cap = c->gpow_cap;
-    if (grow(&c->d_gpow, &cap, gpow.size() * sizeof(u64))) return EXACTO_ERR_HIP;
-    c->gpow_cap = cap;
+    if (c->d_gpow.grow(gpow.size() * sizeof(u64))) return EXACTO_ERR_HIP;
     // the table is host-pageable and d_gpow may still be read by a previous call's kernels
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (int e_ = upload(c, c->d_gpow, gpow.data(), gpow.size() * sizeof(u64))) return e_;
@@ -3623,72 +3577,65 @@ extern "C" int exacto_bfv_apply_automorphism_dev(exacto_ctx* c, const uint64_t* 
     const Ks32Basis& kb = c->kn;
     const bool k32 = d16 && c->ks32 && kb.S > 0 && c->path == EXACTO_PATH_EXACT_RNS;
     if (k32) {
-        size_t cap = c->gk_rs_cap;
-        const int e = ks32_convert_key(c, gk, (size_t)guse, &c->d_gk_rs, &cap, kb.S, kb.d_p32, kb.mac_form);
-        c->gk_rs_cap = cap;
-        if (e) return e;
+        if (int e = ks32_convert_key(c, gk, (size_t)guse, c->d_gk_rs, kb.S, kb.d_p32, kb.mac_form)) return e;
     } else {
-        size_t cap = c->gk_s_cap;
-        if (grow(&c->gk_s, &cap, count * sizeof(u64))) return EXACTO_ERR_HIP;
-        c->gk_s_cap = cap;
+        if (c->gk_s.grow(count * sizeof(u64))) return EXACTO_ERR_HIP;
         launch_shoup_companions(gk, c->gk_s, (long)count, n, L, c->d_primes, c->stream);
         CHECK_LAUNCH();
     }
     const size_t C = std::min<size_t>(c->chunk, B);
-    if (int e = ensure_workspace(c, C)) return e;
     // chunks alternate over the pipeline lanes as in run_mul (the key tables above are made on
     // the main stream before the fork)
-    int nl = 1;
-    if (int e = fork_lanes(c, (long)((B + C - 1) / C), C, &nl)) return e;
-    LaneJoin join{c, nl};
+    LanePass pass;
+    if (int e = pass.begin(c, (long)((B + C - 1) / C), C)) return e;
     for (size_t s0 = 0; s0 < B; s0 += C) {
         const int cnt = (int)std::min(C, B - s0);
-        LaneGuard lane(c, (int)((s0 / C) % (size_t)nl));
+        LaneGuard lane = pass.chunk((long)(s0 / C));
         const u64* src = ct + s0 * 2 * Ln;
         u64* dst = out + s0 * 2 * Ln;
         NttBatch nb{};
         nb.src = src; nb.src_item_stride = 2 * Ln;
-        nb.dst = c->ws_coefQ; nb.dst_item_stride = 2 * Ln;
+        nb.dst = c->ws.coefQ; nb.dst_item_stride = 2 * Ln;
         nb.ppi = 2 * L; nb.prime_base = 0; nb.period = L;
         if (int e = run_ntt(c, nb, (long)cnt * 2 * L, true)) return e;
-        launch_automorph(c->ws_coefQ, 2 * Ln, c->ws_T, 2 * Ln, cnt, 2, n, L, element, c->d_primes, -1, c->stream);
+        launch_automorph(c->ws.coefQ, 2 * Ln, c->ws.T, 2 * Ln, cnt, 2, n, L, element, c->d_primes, -1, c->stream);
         CHECK_LAUNCH();
         if (k32) {
             // digits of sigma(c1); sum_g d_g * r_g over the integers added to (sigma(c0), 0) in the
             // coefficient domain; then both components forward
-            launch_decompose(c->ws_T + Ln, 2 * Ln, c->ws_D, guse, cnt, n, c->d_crt, c->d_primes, L, c->stream,
-                             c->ws_D16);
+            launch_decompose(c->ws.T + Ln, 2 * Ln, c->ws.D, guse, cnt, n, c->d_crt, c->d_primes, L, c->stream,
+                             c->ws.D16);
             CHECK_LAUNCH();
-            launch_rows(c->ws_T + Ln, 2 * Ln, nullptr, 0, Ln, cnt, c->stream);
+            launch_rows(c->ws.T + Ln, 2 * Ln, nullptr, 0, Ln, cnt, c->stream);
             CHECK_LAUNCH();
-            ks32_digits(c->ws_D16, c->ws_DS, cnt, guse, kb.S, c->logn, kb.d_p32, kb.mac_form, c->stream);
-            ks32_mac(c->ws_DS, c->d_gk_rs, c->ws_U, cnt, guse, L, kb.S, n, kb.d_p32, kb.mac_form, c->stream);
-            ks32_crt(c->ws_U, c->ws_T, 2 * Ln, cnt, L, kb.S, c->logn, kb.d_kst, kb.d_p32, c->d_primes, kb.mac_form, c->stream,
+            ks32_digits(c->ws.D16, c->ws.DS, cnt, guse, kb.S, c->logn, kb.d_p32, kb.mac_form, c->stream);
+            ks32_mac(c->ws.DS, c->d_gk_rs, c->ws.U, cnt, guse, L, kb.S, n, kb.d_p32, kb.mac_form, c->stream);
+            ks32_crt(c->ws.U, c->ws.T, 2 * Ln, cnt, L, kb.S, c->logn, kb.d_kst, kb.d_p32, c->d_primes, kb.mac_form, c->stream,
                      c->ks_fpc && kb.fpc_max >= 1);
             CHECK_LAUNCH();
             NttBatch rb{};
-            rb.src = c->ws_T; rb.src_item_stride = 2 * Ln;
+            rb.src = c->ws.T; rb.src_item_stride = 2 * Ln;
             rb.dst = dst; rb.dst_item_stride = 2 * Ln;
             rb.ppi = 2 * L; rb.prime_base = 0; rb.period = L;
             if (int e = run_ntt(c, rb, (long)cnt * 2 * L, false)) return e;
             continue;
         }
         NttBatch c0{};
-        c0.src = c->ws_T; c0.src_item_stride = 2 * Ln;
+        c0.src = c->ws.T; c0.src_item_stride = 2 * Ln;
         c0.dst = dst; c0.dst_item_stride = 2 * Ln;
         c0.ppi = L; c0.prime_base = 0; c0.period = L;
         if (int e = run_ntt(c, c0, (long)cnt * L, false)) return e;
         launch_rows(dst + Ln, 2 * Ln, nullptr, 0, Ln, cnt, c->stream);
-        launch_decompose(c->ws_T + Ln, 2 * Ln, c->ws_D, guse, cnt, n, c->d_crt, c->d_primes, L, c->stream,
-                         d16 ? c->ws_D16 : nullptr);
+        launch_decompose(c->ws.T + Ln, 2 * Ln, c->ws.D, guse, cnt, n, c->d_crt, c->d_primes, L, c->stream,
+                         d16 ? c->ws.D16 : nullptr);
         CHECK_LAUNCH();
-        NttBatch db = contiguous(c->ws_D, cnt, (long)guse * L, 0, L, n);
+        NttBatch db = contiguous(c->ws.D, cnt, (long)guse * L, 0, L, n);
         if (d16) {
-            db.src16 = c->ws_D16;
+            db.src16 = c->ws.D16;
             db.src16_item_stride = (long)guse * n;
         }
         if (int e = run_ntt(c, db, (long)cnt * guse * L, false)) return e;
-        launch_relin_mac(dst, 2 * Ln, c->ws_D, gk, c->gk_s, guse, dst, 2 * Ln, cnt, n, L, c->d_primes, c->stream);
+        launch_relin_mac(dst, 2 * Ln, c->ws.D, gk, c->gk_s, guse, dst, 2 * Ln, cnt, n, L, c->d_primes, c->stream);
         CHECK_LAUNCH();
     }
     return 0;
@@ -3716,9 +3663,7 @@ extern "C" int exacto_bfv_apply_automorphism(exacto_ctx* c, const uint64_t* ct, 
 // ---- plaintext-ciphertext operations and the trace (bfv/eval.rs:468-503, 572-652) ----
 
 static int pl_scratch(exacto_ctx* c, size_t words) {
-    size_t cap = c->pl_cap;
-    if (grow(&c->pl_buf, &cap, words * sizeof(u64))) return EXACTO_ERR_HIP;
-    c->pl_cap = cap;
+    if (c->pl_buf.grow(words * sizeof(u64))) return EXACTO_ERR_HIP;
     return 0;
 }
 
@@ -4204,7 +4149,8 @@ struct BootDebug {
     }
     ~BootDebug() {
         if (dbuf || xbuf || xcc || whit) (void)hipStreamSynchronize(s);
-        free_dev(dbuf); free_dev(xbuf); free_dev(xcc); free_dev(whit);
+        // (raw, like the hipMalloc above: the diagnostic's own blocks stay out of the allocation log)
+        (void)hipFree(dbuf); (void)hipFree(xbuf); (void)hipFree(xcc); (void)hipFree(whit);
     }
     // null source (an earlier allocation failed; the call's rc carries the real error): skipped, so the
     // diagnostic never faults the GPU and hides that error
@@ -4267,11 +4213,7 @@ extern "C" int exacto_bfv_bootstrap_dev(exacto_ctx* o, exacto_ctx* b, const uint
     // finish() to fold a failed synchronisation, e.g. a kernel fault, into the return code).
     const size_t ctw = 2 * Lbn;
     const size_t w_coef = 2 * B * 2 * n, w_flags = (B + 1) / 2, w_c0pt = 2 * B * n;
-    {
-        size_t cap = b->boot_cap;
-        if (grow(&b->boot_buf, &cap, (w_coef + w_flags + w_c0pt + ctw) * sizeof(u64))) return EXACTO_ERR_HIP;
-        b->boot_cap = cap;
-    }
+    if (b->boot_buf.grow((w_coef + w_flags + w_c0pt + ctw) * sizeof(u64))) return EXACTO_ERR_HIP;
     int rc = 0;
     struct Drain {
         exacto_ctx *o, *b;
@@ -4365,10 +4307,8 @@ extern "C" int exacto_bfv_bootstrap_dev(exacto_ctx* o, exacto_ctx* b, const uint
             continue;
         }
         if (!slots) {  // once per call, on the first item that takes the ring path
-            size_t cap = b->boot_slots_cap;
-            if (b->boot_slots_cap < 2 * (size_t)n * ctw * sizeof(u64)) ok(hipStreamSynchronize(b->stream), "sync");
-            if (rc == 0 && grow(&b->boot_slots, &cap, 2 * (size_t)n * ctw * sizeof(u64))) rc = EXACTO_ERR_HIP;
-            b->boot_slots_cap = cap;
+            if (b->boot_slots.bytes() < 2 * (size_t)n * ctw * sizeof(u64)) ok(hipStreamSynchronize(b->stream), "sync");
+            if (rc == 0 && b->boot_slots.grow(2 * (size_t)n * ctw * sizeof(u64))) rc = EXACTO_ERR_HIP;
             if (rc) break;
             slots = b->boot_slots;
             rounded = slots + (size_t)n * ctw;
@@ -4402,15 +4342,14 @@ extern "C" int exacto_bootstrap_key_material(exacto_ctx* o, exacto_ctx* b, const
     if (!o || !b) return invalid_param("null context");
     if (int e = boot_pair_check(o, b)) return e;
     const size_t n = o->n;
-    u64* d = nullptr;
-    HIP_TRY(dev_alloc((void**)&d, (n + b->L * n + n) * sizeof(u64)));
+    DevBuf<u64> d;
+    if (int e = d.alloc((n + b->L * n + n) * sizeof(u64))) return e;
     int rc = upload(o, d, sk, n * sizeof(u64));
     if (rc == 0) rc = exacto_bootstrap_key_material_dev(o, b, d, d + n, d + n + b->L * n);
     if (rc == 0 && (hipMemcpyAsync(boot_sk, d + n, b->L * n * sizeof(u64), hipMemcpyDeviceToHost, o->stream) != hipSuccess ||
                     hipMemcpyAsync(s_pt, d + n + b->L * n, n * sizeof(u64), hipMemcpyDeviceToHost, o->stream) != hipSuccess ||
                     hipStreamSynchronize(o->stream) != hipSuccess))
         rc = fail(EXACTO_ERR_HIP, "HIP error: copy back");
-    (void)hipFree(d);
     return rc;
 }
 
@@ -4532,8 +4471,10 @@ static int batch_ready(exacto_ctx* c) {
         perm[n / 2 + i] = (uint32_t)((k1 % 16) * T + k1 / 16);
         e = e * 3 % (2 * (u64)n);
     }
-    if (!c->d_btw) HIP_TRY(dev_alloc((void**)&c->d_btw, tw.size() * sizeof(uint2)));
-    if (!c->d_bperm) HIP_TRY(dev_alloc((void**)&c->d_bperm, perm.size() * sizeof(uint32_t)));
+    if (!c->d_btw)
+        if (int e_ = c->d_btw.alloc(tw.size() * sizeof(uint2))) return e_;
+    if (!c->d_bperm)
+        if (int e_ = c->d_bperm.alloc(perm.size() * sizeof(uint32_t))) return e_;
     if (int e_ = upload(c, c->d_btw, tw.data(), tw.size() * sizeof(uint2))) return e_;
     if (int e_ = upload(c, c->d_bperm, perm.data(), perm.size() * sizeof(uint32_t))) return e_;
     BatchTab& B = c->batch_tab;
@@ -4709,16 +4650,15 @@ struct exacto_galois_keyset {
     int guse = 0;                 // min(G, num_keys); 0: every element is the identity
     bool k32 = false;             // keys as ks32_convert_key's rows in the narrow 31-bit basis
     int S = 0, mac_form = 0;
-    uint32_t* d_perm = nullptr;   // [R][n]
-    unsigned char* d_ident = nullptr;  // [R]
-    u64 *d_keys = nullptr, *d_keys_s = nullptr;   // limb-wise: [R][guse][2][L][n] and Shoup companions
-    uint32_t* d_rs = nullptr;     // 31-bit path: [R][guse][2L][S][n]
+    DevBuf<uint32_t> d_perm;      // [R][n]
+    DevBuf<unsigned char> d_ident;     // [R]
+    DevBuf<u64> d_keys, d_keys_s;      // limb-wise: [R][guse][2][L][n] and Shoup companions
+    DevBuf<uint32_t> d_rs;        // 31-bit path: [R][guse][2L][S][n]
 };
 
 extern "C" void exacto_galois_keyset_destroy(exacto_galois_keyset* ks) {
     if (!ks) return;
     (void)hipSetDevice(ks->device);
-    free_dev(ks->d_perm); free_dev(ks->d_ident); free_dev(ks->d_keys); free_dev(ks->d_keys_s); free_dev(ks->d_rs);
     delete ks;
 }
 
@@ -4764,8 +4704,8 @@ extern "C" int exacto_galois_keyset_create_dev(exacto_ctx* c, const uint64_t* el
     ks->R = R;
     ks->guse = keyed ? (int)std::min<size_t>(c->G, num_keys) : 0;
     ks->k32 = keyed && hoist_k32(c);
-    HIP_TRY(dev_alloc((void**)&ks->d_perm, perm.size() * sizeof(uint32_t)));
-    HIP_TRY(dev_alloc((void**)&ks->d_ident, (R + 7) / 8 * 8));
+    if (int e = ks->d_perm.alloc(perm.size() * sizeof(uint32_t))) return e;
+    if (int e = ks->d_ident.alloc((R + 7) / 8 * 8)) return e;
     if (int e = upload(c, ks->d_perm, perm.data(), perm.size() * sizeof(uint32_t))) return e;
     if (int e = upload(c, ks->d_ident, ident.data(), R)) return e;
     const size_t guse = (size_t)ks->guse;
@@ -4773,7 +4713,7 @@ extern "C" int exacto_galois_keyset_create_dev(exacto_ctx* c, const uint64_t* el
         const Ks32Basis& kb = c->kn;   // the narrow basis: its bound holds for any key (as the single call)
         ks->S = kb.S; ks->mac_form = kb.mac_form;
         const long rows = (long)guse * 2 * L;
-        HIP_TRY(dev_alloc((void**)&ks->d_rs, R * (size_t)rows * kb.S * n * sizeof(uint32_t)));
+        if (int e = ks->d_rs.alloc(R * (size_t)rows * kb.S * n * sizeof(uint32_t))) return e;
         Scratch kc;
         HIP_TRY(kc.alloc((size_t)rows * n * sizeof(u64), c->stream, c->pool, c->debug_scratch));
         for (size_t r = 0; r < R; ++r) {
@@ -4789,8 +4729,8 @@ extern "C" int exacto_galois_keyset_create_dev(exacto_ctx* c, const uint64_t* el
         }
     } else if (keyed) {
         const size_t per = guse * 2 * (size_t)Ln;
-        HIP_TRY(dev_alloc((void**)&ks->d_keys, R * per * sizeof(u64)));
-        HIP_TRY(dev_alloc((void**)&ks->d_keys_s, R * per * sizeof(u64)));
+        if (int e = ks->d_keys.alloc(R * per * sizeof(u64))) return e;
+        if (int e = ks->d_keys_s.alloc(R * per * sizeof(u64))) return e;
         for (size_t r = 0; r < R; ++r) {
             if (ident[r])
                 launch_rows(ks->d_keys + r * per, 0, nullptr, 0, (long)per, 1, c->stream);
@@ -4813,12 +4753,10 @@ extern "C" int exacto_galois_keyset_create(exacto_ctx* c, const uint64_t* elemen
     if (!gks || num_keys == 0 || R == 0 || !elements || !out)   // nothing to stage: the device form's checks
         return exacto_galois_keyset_create_dev(c, elements, R, nullptr, num_keys, out);
     const size_t bytes = R * num_keys * 2 * c->L * poly_bytes(c);
-    u64* d = nullptr;
-    HIP_TRY(dev_alloc((void**)&d, bytes));
-    int rc = upload(c, d, gks, bytes);
-    if (rc == 0) rc = exacto_galois_keyset_create_dev(c, elements, R, d, num_keys, out);
-    free_dev(d);
-    return rc;
+    DevBuf<u64> d;
+    if (int e = d.alloc(bytes)) return e;
+    if (int e = upload(c, d, gks, bytes)) return e;
+    return exacto_galois_keyset_create_dev(c, elements, R, d, num_keys, out);
 }
 
 static int hoist_check(exacto_ctx* c, const exacto_galois_keyset* ks) {
@@ -4854,33 +4792,31 @@ static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* 
     if (k32) C = std::max<size_t>(1, C * 2 / (size_t)(kb.S + (lt ? 2 : 0)));
     const size_t nblk = (size_t)((Ln + 255) / 256);
     C = std::max<size_t>(1, std::min<size_t>(C, ((size_t)1 << 30) / (nblk * ks->R)));
-    if (int e = ensure_workspace(c, C)) return e;
     const long nchunks = (long)((B + C - 1) / C);
-    const int nl_max = (c->dual && !c->prof) ? (int)std::min<long>(c->lanes, nchunks) : 1;
-    // per-lane scratch, allocated before the fork and released after the join (declared before LaneJoin)
+    const int nl_max = LanePass::count(c, nchunks);
+    // per-lane scratch, declared before the LanePass: allocated before the fork, released after the join
     const size_t u_words = k32 ? C * ks->R * 2 * L * (size_t)kb.S * n : 0;            // uint32
     const size_t h_words = (k32 && lt) ? C * ks->R * 2 * (size_t)Ln : 0;              // u64
     Scratch us, hs;
     if (u_words) HIP_TRY(us.alloc(u_words * nl_max * sizeof(uint32_t), c->stream, c->pool, c->debug_scratch));
     if (h_words) HIP_TRY(hs.alloc(h_words * nl_max * sizeof(u64), c->stream, c->pool, c->debug_scratch));
-    int nl = 1;
-    if (int e = fork_lanes(c, nchunks, C, &nl)) return e;
-    LaneJoin join{c, nl};
+    LanePass pass;
+    if (int e = pass.begin(c, nchunks, C)) return e;
     for (size_t s0 = 0; s0 < B; s0 += C) {
         const int cnt = (int)std::min(C, B - s0);
-        const int li = (int)((s0 / C) % (size_t)nl);
-        LaneGuard lane(c, li);
+        const int li = (int)((s0 / C) % (size_t)pass.lanes());
+        LaneGuard lane = pass.chunk((long)(s0 / C));
         const u64* src = ct + s0 * 2 * Ln;
         u64* dst = out + s0 * 2 * Ln * (lt ? 1 : ks->R);
         if (guse > 0) {
             // c1 alone back to coefficients, its exact CRT and gadget digits, one digit transform
             NttBatch nb{};
             nb.src = src + Ln; nb.src_item_stride = 2 * Ln;
-            nb.dst = c->ws_coefQ; nb.dst_item_stride = Ln;
+            nb.dst = c->ws.coefQ; nb.dst_item_stride = Ln;
             nb.ppi = L; nb.prime_base = 0; nb.period = L;
             if (int e = run_ntt(c, nb, (long)cnt * L, true)) return e;
-            launch_decompose(c->ws_coefQ, Ln, c->ws_D, guse, cnt, n, c->d_crt, c->d_primes, L, c->stream,
-                             d16 ? c->ws_D16 : nullptr);
+            launch_decompose(c->ws.coefQ, Ln, c->ws.D, guse, cnt, n, c->d_crt, c->d_primes, L, c->stream,
+                             d16 ? c->ws.D16 : nullptr);
             CHECK_LAUNCH();
         }
         if (k32) {
@@ -4888,14 +4824,14 @@ static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* 
             u64* H = lt ? hs.as<u64>() + (size_t)li * h_words : dst;
             {
                 ProfScope pd(c, PK_KS_DIGITS, (u64)cnt * guse * kb.S, (2.0 + 4.0 * kb.S) * n * (double)cnt * guse);
-                ks32_digits(c->ws_D16, c->ws_DS, cnt, guse, kb.S, c->logn, kb.d_p32, kb.mac_form, c->stream);
+                ks32_digits(c->ws.D16, c->ws.DS, cnt, guse, kb.S, c->logn, kb.d_p32, kb.mac_form, c->stream);
             }
             // The basis bound of setup_ks32 covers sigma(d) unchanged: sigma permutes a digit's coefficients
             // up to sign, so the digit magnitudes, and with them |sum_g sigma(d_g) * r_g|, are the same.
             {
                 ProfScope pm(c, PK_KS_MAC, (u64)cnt * R * 2 * L * kb.S,
                              4.0 * n * kb.S * ((double)cnt * R * (guse + 2 * L) + (double)R * guse * 2 * L));
-                ks32_mac_hoist(c->ws_DS, ks->d_rs, U, ks->d_perm, ks->d_ident, cnt, R, guse, L, kb.S, n, kb.d_p32,
+                ks32_mac_hoist(c->ws.DS, ks->d_rs, U, ks->d_perm, ks->d_ident, cnt, R, guse, L, kb.S, n, kb.d_p32,
                                kb.mac_form, c->stream);
             }
             CHECK_LAUNCH();
@@ -4919,9 +4855,9 @@ static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* 
             continue;
         }
         if (guse > 0) {
-            NttBatch db = contiguous(c->ws_D, cnt, (long)guse * L, 0, L, n);
+            NttBatch db = contiguous(c->ws.D, cnt, (long)guse * L, 0, L, n);
             if (d16) {
-                db.src16 = c->ws_D16;
+                db.src16 = c->ws.D16;
                 db.src16_item_stride = (long)guse * n;
             }
             if (int e = run_ntt(c, db, (long)cnt * guse * L, false)) return e;
@@ -4929,7 +4865,7 @@ static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* 
         {
             ProfScope pm(c, PK_RELIN_MAC, (u64)cnt * R * 2 * L,
                          8.0 * Ln * ((double)cnt * R * (guse + 1 + (lt ? 0 : 2)) + (double)R * guse * 4));
-            launch_hoist_mac(lt, src, c->ws_D, ks->d_keys, ks->d_keys_s, ks->d_perm, ks->d_ident,
+            launch_hoist_mac(lt, src, c->ws.D, ks->d_keys, ks->d_keys_s, ks->d_perm, ks->d_ident,
                              lt ? c->pl_buf : nullptr, dst, R, guse, cnt, n, L, c->d_primes, c->stream);
         }
         CHECK_LAUNCH();
@@ -4979,7 +4915,7 @@ static int batch_encrypt_dev(exacto_ctx* c, const uint64_t* values, const uint64
     if (B == 0) return 0;
     if ((uintptr_t)values & 15) return invalid_param("batch: buffers must be 16-byte aligned");
     const size_t C = std::min<size_t>(c->chunk, B), n = (size_t)c->n;
-    if (grow(&c->batch_buf, &c->batch_cap, C * poly_bytes(c))) return EXACTO_ERR_HIP;
+    if (c->batch_buf.grow(C * poly_bytes(c))) return EXACTO_ERR_HIP;
     for (size_t i0 = 0; i0 < B; i0 += C) {
         const size_t cnt = std::min(C, B - i0);
         launch_batch_transform(true, values + i0 * n, c->batch_buf, (long)cnt, c->logn, c->batch_tab, c->batch_form,
@@ -5012,7 +4948,7 @@ extern "C" int exacto_batch_decrypt_dev(exacto_ctx* c, const uint64_t* ct, size_
     if ((uintptr_t)values & 15) return invalid_param("batch: buffers must be 16-byte aligned");
     const size_t C = std::min<size_t>(c->chunk, B), n = (size_t)c->n;
     const long stride = (long)polys * c->L * c->n;
-    if (grow(&c->batch_buf, &c->batch_cap, C * poly_bytes(c))) return EXACTO_ERR_HIP;
+    if (c->batch_buf.grow(C * poly_bytes(c))) return EXACTO_ERR_HIP;
     for (size_t i0 = 0; i0 < B; i0 += C) {
         const size_t cnt = std::min(C, B - i0);
         if (int e = decrypt_batch(c, ct + i0 * (size_t)stride, polys, stride, sk, c->batch_buf, cnt)) return e;
@@ -5145,7 +5081,7 @@ static int dbfv_batch_encrypt_dev(exacto_ctx* c, size_t d, uint64_t base, uint64
     if (B == 0) return 0;
     if ((uintptr_t)values & 15) return invalid_param("dbfv batch: buffers must be 16-byte aligned");
     const size_t C = std::min<size_t>(c->chunk, B), n = (size_t)c->n;
-    if (grow(&c->batch_buf, &c->batch_cap, C * d * poly_bytes(c))) return EXACTO_ERR_HIP;
+    if (c->batch_buf.grow(C * d * poly_bytes(c))) return EXACTO_ERR_HIP;
     for (size_t i0 = 0; i0 < B; i0 += C) {
         const size_t cnt = std::min(C, B - i0);
         dbfv_batch_launch(c, true, values + i0 * n, c->batch_buf, cnt, d, base, plain);
@@ -5182,9 +5118,7 @@ extern "C" int exacto_dbfv_batch_decrypt_dev(exacto_ctx* c, size_t d, uint64_t b
     if ((uintptr_t)values & 15) return invalid_param("dbfv batch: buffers must be 16-byte aligned");
     const size_t C = std::min<size_t>(c->chunk, B), n = (size_t)c->n;
     const long stride = 2L * c->L * c->n;
-    size_t cap = c->dig_bytes;
-    if (grow(&c->dig_buf, &cap, C * d * poly_bytes(c))) return EXACTO_ERR_HIP;
-    c->dig_bytes = cap;
+    if (c->dig_buf.grow(C * d * poly_bytes(c))) return EXACTO_ERR_HIP;
     for (size_t i0 = 0; i0 < B; i0 += C) {
         const size_t cnt = std::min(C, B - i0);
         if (int e = decrypt_batch(c, ct + i0 * d * (size_t)stride, 2, stride, sk, c->dig_buf, cnt * d)) return e;
@@ -5430,13 +5364,11 @@ extern "C" int exacto_dbfv_linear_map_dev(exacto_ctx* c, size_t d_in, size_t d_o
         // the table is host-pageable and d_lin may still be read by a previous call's kernel
         HIP_TRY(hipStreamSynchronize(c->stream));
         c->lin_host.clear();
-        size_t cap = c->lin_cap;
-        if (grow(&c->d_lin, &cap, tab.size() * sizeof(u64))) return EXACTO_ERR_HIP;
-        c->lin_cap = cap;
+        if (c->d_lin.grow(tab.size() * sizeof(u64))) return EXACTO_ERR_HIP;
         if (int e_ = upload(c, c->d_lin, tab.data(), tab.size() * sizeof(u64))) return e_;
         c->lin_host = tab;
     }
-    launch_dbfv_linmap(in, out, reinterpret_cast<const LinTerm*>(c->d_lin), (int)E, (int)d_in, (int)d_out, (long)B,
+    launch_dbfv_linmap(in, out, reinterpret_cast<const LinTerm*>(c->d_lin.get()), (int)E, (int)d_in, (int)d_out, (long)B,
                        (int)polys, c->n, L, c->d_primes, c->stream);
     CHECK_LAUNCH();
     return 0;
@@ -5846,8 +5778,8 @@ static int rccl_agree(exacto_ctx* c, void* comm, u64 mine, u64 ok, bool* agreed,
     *agreed = false;
     int nr = 0;
     RCCL_TRY(rccl().comm_count((ncclComm_t)comm, &nr));
-    u64* dev = nullptr;
-    HIP_TRY(hipMalloc((void**)&dev, sizeof(u64) * 2 * (nr + 1)));
+    DevBuf<u64> dev;
+    if (int e = dev.alloc(sizeof(u64) * 2 * (nr + 1))) return e;
     std::vector<u64> host(2 * (size_t)(nr + 1));
     host[0] = mine;
     host[1] = ok;
@@ -5864,9 +5796,12 @@ static int rccl_agree(exacto_ctx* c, void* comm, u64 mine, u64 ok, bool* agreed,
             if (!rc) rc = fail(EXACTO_ERR_HIP, "HIP error: agreement header read-back");
         }
     }
-    if (rc) return rc;   // a timed-out all-gather may still own `dev`: leave it (the process is ending)
+    if (rc) {   // a timed-out all-gather may still own `dev`, and a release would wait for it: leave the
+                // block to a holder that is never destroyed (the process is ending)
+        (void)new DevBuf<u64>(std::move(dev));
+        return rc;
+    }
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(dev);
     for (int r = 0; r < nr; ++r) {
         if (!host[2 + 2 * r + 1]) {
             *why = "rank " + std::to_string(r) + " rejected the call";
