@@ -162,6 +162,14 @@ _SIGS = [
       for kind in ("sk", "pk") for sfx in ("", "_dev")],
     ("exacto_dbfv_batch_decrypt", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
     ("exacto_dbfv_batch_decrypt_dev", [_P, _SZ, _U64, _U64, _P, _P, _P, _SZ], C.c_int),
+    *[(f"exacto_dbfv_plain_mul_sum{sfx}", [_P, _SZ, _U64, _U64, _P, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _P], C.c_int)
+      for sfx in ("", "_dev")],
+    *[(f"exacto_dbfv_plain_mul{sfx}", [_P, _SZ, _U64, _U64, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P], C.c_int)
+      for sfx in ("", "_dev")],
+    *[(f"exacto_dbfv_plain_{op}{sfx}", [_P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ], C.c_int)
+      for op in ("add", "sub") for sfx in ("", "_dev")],
+    ("exacto_ctx_set_plain_terms", [_P, _SZ], C.c_int),
+    ("exacto_dbfv_plain_limits", [_P, C.POINTER(_SZ), C.POINTER(_SZ)], C.c_int),
     ("exacto_bfv_plain_mul", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_plain_mul_dev", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_plain_add", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
@@ -1050,6 +1058,117 @@ class HipContext:
         check(self._lib.exacto_dbfv_batch_decrypt(self._h, d, base, plain, ct.ctypes.data, sk.ctypes.data,
                                                   out.ctypes.data, ct.shape[0]))
         return out
+
+    # ---- dBFV plaintext products (exacto_dbfv_plain_*): public wide operands times dBFV ciphertexts, exacto_hip.h
+    def set_plain_terms(self, terms: int):
+        """Terms of a dBFV plaintext product lifted at a time (0: the default); no result depends on it."""
+        check(self._lib.exacto_ctx_set_plain_terms(self._h, terms))
+
+    def dbfv_plain_limits(self) -> tuple[int, int]:
+        """(products one accumulator of the product kernel takes between two reductions, term chunk)."""
+        f, t = _SZ(0), _SZ(0)
+        check(self._lib.exacto_dbfv_plain_limits(self._h, C.byref(f), C.byref(t)))
+        return int(f.value), int(t.value)
+
+    def dbfv_plain_mul_sum(self, d, base, plain, cts, pts, depth_ct=None):
+        """cts [B][K][d][polys][L][n], pts [B or 1][K][d][n] -> (out [B][d][polys][L][n], mul_depth [B]):
+        reduce(sum_k pts[k] * cts[k]) over the digit vectors."""
+        cts, pts = _u64(cts), _u64(pts)
+        if cts.ndim != 6 or pts.ndim != 4:
+            raise ValueError("cts must be [B][K][d][polys][L][n] and pts [B or 1][K][d][n]")
+        B, K, polys = cts.shape[0], cts.shape[1], cts.shape[3]
+        out = np.zeros((B, d) + cts.shape[3:], dtype=np.uint64)
+        dc = np.ascontiguousarray(depth_ct, dtype=np.uint32).reshape(B, K) if depth_ct is not None else None
+        dout = np.zeros(B, dtype=np.uint32)
+        check(self._lib.exacto_dbfv_plain_mul_sum(self._h, d, base, plain, cts.ctypes.data, K, polys, pts.ctypes.data,
+                                                  pts.shape[0], out.ctypes.data, B, _ptr(dc), dout.ctypes.data))
+        return out, dout
+
+    def dbfv_plain_mul(self, d, base, plain, ct, pt, depth_ct=None):
+        """ct [B][d][polys][L][n], pt [B or 1][d][n] -> (out, mul_depth [B]): dbfv_plain_mul_sum with K = 1."""
+        ct, pt = _u64(ct), _u64(pt)
+        if ct.ndim != 5 or pt.ndim != 3:
+            raise ValueError("ct must be [B][d][polys][L][n] and pt [B or 1][d][n]")
+        B = ct.shape[0]
+        out = np.zeros_like(ct)
+        dc = self._depths(depth_ct, B)
+        dout = np.zeros(B, dtype=np.uint32)
+        check(self._lib.exacto_dbfv_plain_mul(self._h, d, base, plain, ct.ctypes.data, ct.shape[2], pt.ctypes.data,
+                                              pt.shape[0], out.ctypes.data, B, _ptr(dc), dout.ctypes.data))
+        return out, dout
+
+    def _dbfv_plain_addsub(self, fn, ct, pt):
+        ct, pt = _u64(ct), _u64(pt)
+        if ct.ndim != 5 or pt.ndim != 3:
+            raise ValueError("ct must be [B][d][polys][L][n] and pt [B or 1][d][n]")
+        out = np.zeros_like(ct)
+        check(fn(self._h, ct.shape[1], ct.ctypes.data, ct.shape[2], pt.ctypes.data, pt.shape[0], out.ctypes.data,
+                 ct.shape[0]))
+        return out
+
+    def dbfv_plain_add(self, ct, pt) -> np.ndarray:
+        """ct [B][d][polys][L][n] + pt [B or 1][d][n]: bfv_plain_add limb by limb (c0 + Delta m)."""
+        return self._dbfv_plain_addsub(self._lib.exacto_dbfv_plain_add, ct, pt)
+
+    def dbfv_plain_sub(self, ct, pt) -> np.ndarray:
+        """ct - pt limb by limb (c0 - Delta m)."""
+        return self._dbfv_plain_addsub(self._lib.exacto_dbfv_plain_sub, ct, pt)
+
+    def dbfv_batch_plain_mul(self, d, base, plain, ct, values, depth_ct=None):
+        """Slot-wise ct * values mod p: values [B or 1][n] slot-encoded on the device (dbfv_batch_encode), then
+        dbfv_plain_mul.  Returns (out, mul_depth [B])."""
+        return self.dbfv_plain_mul(d, base, plain, ct, self.dbfv_batch_encode(d, base, plain, values), depth_ct)
+
+    def dbfv_batch_plain_dot(self, d, base, plain, cts, values, depth_ct=None):
+        """Slot-wise sum_k cts[k] * values[k] mod p: cts [B][K][d][polys][L][n], values [B or 1][K][n]."""
+        v = _u64(values)
+        if v.ndim != 3 or v.shape[2] != self.n:
+            raise ValueError(f"values must be a [B or 1][K][{self.n}] array")
+        pts = self.dbfv_batch_encode(d, base, plain, v.reshape(-1, self.n)).reshape(v.shape[0], v.shape[1], d, self.n)
+        return self.dbfv_plain_mul_sum(d, base, plain, cts, pts, depth_ct)
+
+    def dbfv_batch_plain_add(self, d, base, plain, ct, values) -> np.ndarray:
+        """Slot-wise ct + values mod p (values [B or 1][n])."""
+        return self.dbfv_plain_add(ct, self.dbfv_batch_encode(d, base, plain, values))
+
+    def dbfv_batch_plain_sub(self, d, base, plain, ct, values) -> np.ndarray:
+        """Slot-wise ct - values mod p (values [B or 1][n])."""
+        return self.dbfv_plain_sub(ct, self.dbfv_batch_encode(d, base, plain, values))
+
+    def dbfv_plain_mul_sum_dev(self, d, base, plain, cts, K, polys, pts, pt_batch, out, batch, depth_ct=None):
+        dc = np.ascontiguousarray(depth_ct, dtype=np.uint32) if depth_ct is not None else None    # [batch][K]
+        check(self._lib.exacto_dbfv_plain_mul_sum_dev(self._h, d, base, plain, self._p(cts), K, polys, self._p(pts),
+                                                      pt_batch, self._p(out), batch, _ptr(dc), None))
+
+    def dbfv_plain_mul_dev(self, d, base, plain, ct, polys, pt, pt_batch, out, batch, depth_ct=None):
+        dc = self._depths(depth_ct, batch)
+        check(self._lib.exacto_dbfv_plain_mul_dev(self._h, d, base, plain, self._p(ct), polys, self._p(pt), pt_batch,
+                                                  self._p(out), batch, _ptr(dc), None))
+
+    def dbfv_plain_add_dev(self, d, ct, polys, pt, pt_batch, out, batch):
+        check(self._lib.exacto_dbfv_plain_add_dev(self._h, d, self._p(ct), polys, self._p(pt), pt_batch, self._p(out),
+                                                  batch))
+
+    def dbfv_plain_sub_dev(self, d, ct, polys, pt, pt_batch, out, batch):
+        check(self._lib.exacto_dbfv_plain_sub_dev(self._h, d, self._p(ct), polys, self._p(pt), pt_batch, self._p(out),
+                                                  batch))
+
+    def dbfv_batch_plain_mul_dev(self, d, base, plain, ct, polys, values, pt_batch, pt, out, batch):
+        """values [pt_batch][n] -> pt [pt_batch][d][n] (dbfv_batch_encode_dev), then dbfv_plain_mul_dev into out."""
+        self.dbfv_batch_encode_dev(d, base, plain, values, pt, pt_batch)
+        self.dbfv_plain_mul_dev(d, base, plain, ct, polys, pt, pt_batch, out, batch)
+
+    def dbfv_batch_plain_dot_dev(self, d, base, plain, cts, K, polys, values, pt_batch, pts, out, batch):
+        """values [pt_batch][K][n] -> pts [pt_batch][K][d][n], then dbfv_plain_mul_sum_dev into out."""
+        self.dbfv_batch_encode_dev(d, base, plain, values, pts, pt_batch * K)
+        self.dbfv_plain_mul_sum_dev(d, base, plain, cts, K, polys, pts, pt_batch, out, batch)
+
+    def dbfv_batch_plain_add_dev(self, d, base, plain, ct, polys, values, pt_batch, pt, out, batch, sub=False):
+        self.dbfv_batch_encode_dev(d, base, plain, values, pt, pt_batch)
+        (self.dbfv_plain_sub_dev if sub else self.dbfv_plain_add_dev)(d, ct, polys, pt, pt_batch, out, batch)
+
+    def dbfv_batch_plain_sub_dev(self, d, base, plain, ct, polys, values, pt_batch, pt, out, batch):
+        self.dbfv_batch_plain_add_dev(d, base, plain, ct, polys, values, pt_batch, pt, out, batch, sub=True)
 
     def dbfv_batch_encode_dev(self, d, base, plain, values, pt, batch):
         check(self._lib.exacto_dbfv_batch_encode_dev(self._h, d, base, plain, self._p(values), self._p(pt), batch))

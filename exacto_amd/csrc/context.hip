@@ -5,6 +5,7 @@
 // HBM, the exact-CRT tables, the resident relinearisation key and a chunked
 // workspace.  Every `_dev` entry point only enqueues kernels on the context stream.
 #include <algorithm>
+#include <array>
 #include <cxxabi.h>
 #include <dlfcn.h>
 #include <chrono>
@@ -401,6 +402,9 @@ struct exacto_ctx {
     DevBuf<u64> enc_buf;
     DevBuf<u64> d_lin;  // terms of the last dBFV linear map, LinTerm [E][L]
     std::vector<u64> lin_host;  // what d_lin holds
+    DevBuf<u64> d_dp;   // fold digits or pair list of the last dBFV plaintext product (dbfv_plain_tables)
+    std::vector<u64> dp_host;   // what d_dp holds
+    size_t plain_terms = 64;    // dBFV plaintext products: terms lifted into pl_buf at a time
     DevBuf<u64> gk_s;  // Shoup companions of the Galois key of the last automorphism call
     DevBuf<uint32_t> d_gk_rs;  // ks32: Galois key of the last automorphism call in the 31-bit basis
     DevBuf<u64> pl_buf;  // lifted plaintexts / monomial scratch
@@ -1245,6 +1249,12 @@ extern "C" int exacto_ctx_set_stream(exacto_ctx* c, void* s) {
 extern "C" int exacto_ctx_set_chunk(exacto_ctx* c, size_t chunk) {
     if (!c) return invalid_param("null context");
     c->chunk = chunk == 0 ? 128 : chunk;
+    return 0;
+}
+
+extern "C" int exacto_ctx_set_plain_terms(exacto_ctx* c, size_t terms) {
+    if (!c) return invalid_param("null context");
+    c->plain_terms = terms == 0 ? 64 : terms;
     return 0;
 }
 
@@ -5459,6 +5469,238 @@ extern "C" int exacto_dbfv_div_by_base(exacto_ctx* c, size_t d, uint64_t base, u
     return host_call(c, {{in, bytes}}, bytes, out, [&](std::vector<u64*>& dv, u64* o) {
         return exacto_dbfv_div_by_base_dev(c, d, base, plain, dv[0], o, B, new_plain);
     });
+}
+
+// ============================================================== dBFV plaintext products
+// out = reduce(sum_k pt_k * ct_k) over digit vectors (dbfv_plain.hip): bfv_plain_mul per digit pair
+// (bfv/eval.rs:468-486), bfv_add by i + j and over k, reduce (reduction.rs:15-93), in one kernel.
+
+// Products a 128-bit accumulator of dbfv_plain.hip takes between two reductions: 2^(128 - 2s) - 2 for the
+// largest prime's bit length s <= 62 (one slot for the carried residue, one to spare), at most 2^20.
+static int dbfv_plain_flush_products(const exacto_ctx* c) {
+    int s = 1;
+    for (int l = 0; l < c->L; ++l) s = std::max(s, 64 - __builtin_clzll(c->primes[l]));
+    const int e = 128 - 2 * s;
+    return e >= 20 ? (1 << 20) : (1 << e) - 2;
+}
+
+extern "C" int exacto_dbfv_plain_limits(exacto_ctx* c, size_t* flush_products, size_t* chunk_terms) {
+    if (!c) return invalid_param("null context");
+    if (flush_products) *flush_products = (size_t)dbfv_plain_flush_products(c);
+    if (chunk_terms) *chunk_terms = c->plain_terms;
+    return 0;
+}
+
+// The kernel's host tables in d_dp behind a two-word header {d, form}: d <= DP_MAX_D: rep[m - d][i] mod
+// q_l as [L][d - 1][d]; above, the list form's pairs [E][L].  *live: the high limbs with a non-zero
+// representative (a pair whose wide limb has none is never formed).
+static int dbfv_plain_tables(exacto_ctx* c, size_t d, u64 base, u64 plain, unsigned* live, int* E) {
+    const auto reps = small_reps(base, d, plain);
+    const int L = c->L;
+    const bool regs = d <= DP_MAX_D;
+    std::vector<u64> tab{(u64)d, regs ? 0u : 1u};
+    *live = 0;
+    *E = 0;
+    if (regs) {
+        for (size_t m = 0; m + 1 < d; ++m)
+            for (size_t i = 0; i < d; ++i)
+                if (reps[m][i]) *live |= 1u << m;
+        for (int l = 0; l < L; ++l)
+            for (size_t m = 0; m + 1 < d; ++m)
+                for (size_t i = 0; i < d; ++i) tab.push_back((u64)reps[m][i] % c->primes[l]);
+    } else {
+        static_assert(sizeof(DpPair) == 3 * sizeof(u64), "DpPair is three words: s, {ci, pi}, {last, pad}");
+        auto pair = [&](u64 coef, size_t ci, size_t pi, bool last) {
+            for (int l = 0; l < L; ++l) {
+                const u64 w[3] = {coef % c->primes[l], (u64)ci | ((u64)pi << 32), last ? 1u : 0u};
+                tab.insert(tab.end(), w, w + 3);
+            }
+            ++*E;
+        };
+        for (size_t i = 0; i < d; ++i) {
+            std::vector<std::array<u64, 3>> row;
+            for (size_t pi = 0; pi < d; ++pi)
+                for (size_t ci = 0; ci < d; ++ci) {
+                    const size_t m = pi + ci;
+                    const u64 coef = m == i ? 1 : m >= d ? (u64)reps[m - d][i] : 0;
+                    if (coef) row.push_back({coef, (u64)ci, (u64)pi});
+                }
+            if (row.empty()) pair(0, 0, 0, true);
+            for (size_t e = 0; e < row.size(); ++e) pair(row[e][0], row[e][1], row[e][2], e + 1 == row.size());
+        }
+    }
+    if (tab != c->dp_host) {
+        // the table is host-pageable and d_dp may still be read by a previous call's kernel
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->dp_host.clear();
+        if (c->d_dp.grow(tab.size() * sizeof(u64))) return EXACTO_ERR_HIP;
+        if (int e_ = upload(c, c->d_dp, tab.data(), tab.size() * sizeof(u64))) return e_;
+        c->dp_host = tab;
+    }
+    return 0;
+}
+
+static bool ranges_overlap(const u64* a, size_t aw, const u64* b, size_t bw) { return a < b + bw && b < a + aw; }
+
+// The checks of exacto_dbfv_plain_mul_sum[_dev], in the header's order
+static int dbfv_plain_mul_check(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* cts, size_t K,
+                                size_t polys, const uint64_t* pts, size_t pt_batch, const uint64_t* out, size_t B,
+                                const uint32_t* depth_ct, bool dev) {
+    if (int e = check_ctx(c)) return e;
+    if (!cts || !pts || !out) return invalid_param("null argument");
+    if (K == 0) return invalid_param("mismatched ct/pt lengths");
+    if (polys == 0) return invalid_param("ciphertext has no components");
+    if (pt_batch != 1 && pt_batch != B) return invalid_param("plaintext batch must be 1 or the batch");
+    if (int e = dbfv_params_check(d, base, plain)) return e;
+    if (d > 64) return invalid_param("plaintext product larger than 64 digits");
+    for (size_t i = 0; depth_ct && i < B * K; ++i)
+        if (depth_ct[i] + 1 > 1)
+            return fail(EXACTO_ERR_NOT_IMPLEMENTED, "not yet implemented: chained dBFV multiplication requires "
+                                                    "ciphertext-level lattice reduction (paper §4.6.2)");
+    if (dev && (((uintptr_t)cts | (uintptr_t)pts | (uintptr_t)out) & 15))
+        return invalid_param("dbfv plain: buffers must be 16-byte aligned");
+    const size_t n = (size_t)c->n, limb = polys * c->L * n;
+    if (ranges_overlap(out, B * d * limb, cts, B * K * d * limb) || ranges_overlap(out, B * d * limb, pts, pt_batch * K * d * n))
+        return invalid_param("dbfv plain: the output must not overlap an input");
+    if (std::min<size_t>(c->chunk, B) * polys * c->L > ((size_t)1 << 31) / n * 256) return invalid_param("batch too large");
+    return 0;
+}
+
+// pt rows [rows][n] (any u64) -> NTT(pt mod q_l) as [rows][L][n] at dst (inside pl_buf)
+static int lift_plain_rows(exacto_ctx* c, const u64* pt, long rows, u64* dst) {
+    launch_scale_plain(pt, nullptr, dst, rows, c->n, c->L, c->d_primes, c->stream);
+    CHECK_LAUNCH();
+    return ntt_items(c, dst, rows, (long)c->L * c->n, c->L);
+}
+
+extern "C" int exacto_dbfv_plain_mul_sum_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
+                                             const uint64_t* cts, size_t K, size_t polys, const uint64_t* pts,
+                                             size_t pt_batch, uint64_t* out, size_t B, const uint32_t* depth_ct,
+                                             uint32_t* depth_out) {
+    if (int e = dbfv_plain_mul_check(c, d, base, plain, cts, K, polys, pts, pt_batch, out, B, depth_ct, true)) return e;
+    if (B == 0) return 0;
+    unsigned live = 0;
+    int E = 0;
+    if (int e = dbfv_plain_tables(c, d, base, plain, &live, &E)) return e;
+    const size_t n = (size_t)c->n, Ln = (size_t)c->L * n;
+    const size_t ct_term = d * polys * Ln, ct_item = K * ct_term;
+    const bool shared = pt_batch == 1;
+    // term chunks of at most plain_terms terms (a later chunk adds into out), items in chunks of the
+    // context's chunk; a shared plaintext is lifted once per term chunk, a per-item one per item chunk
+    const size_t Kc = std::min(K, c->plain_terms), C = std::min<size_t>(c->chunk, B);
+    if (int e = pl_scratch(c, (shared ? 1 : C) * Kc * d * Ln)) return e;
+    DbfvPlainArgs a{};
+    a.ct_item_stride = (long)ct_item; a.ct_term_stride = (long)ct_term;
+    a.d = (int)d; a.polys = (int)polys; a.n = c->n; a.L = c->L;
+    a.flush = dbfv_plain_flush_products(c);
+    a.live = live;
+    a.fold = c->d_dp.get() + 2;
+    a.pairs = reinterpret_cast<const DpPair*>(c->d_dp.get() + 2);
+    a.E = E;
+    a.primes = c->d_primes;
+    a.pl = c->pl_buf;
+    for (size_t k0 = 0; k0 < K; k0 += Kc) {
+        const size_t kc = std::min(Kc, K - k0);
+        a.K = (int)kc;
+        a.accum = k0 != 0;
+        a.pl_term_stride = (long)(d * Ln);
+        a.pl_item_stride = shared ? 0 : (long)(kc * d * Ln);
+        for (size_t i0 = 0; i0 < B; i0 += C) {
+            const size_t cnt = std::min(C, B - i0);
+            if (shared) {
+                if (i0 == 0)
+                    if (int e = lift_plain_rows(c, pts + k0 * d * n, (long)(kc * d), c->pl_buf)) return e;
+            } else if (kc == K) {
+                if (int e = lift_plain_rows(c, pts + i0 * K * d * n, (long)(cnt * K * d), c->pl_buf)) return e;
+            } else {
+                for (size_t i = 0; i < cnt; ++i)
+                    if (int e = lift_plain_rows(c, pts + ((i0 + i) * K + k0) * d * n, (long)(kc * d),
+                                                c->pl_buf + i * kc * d * Ln))
+                        return e;
+            }
+            a.cts = cts + i0 * ct_item + k0 * ct_term;
+            a.out = out + i0 * d * polys * Ln;
+            a.items = (long)cnt;
+            launch_dbfv_plain_mul(a, c->stream);
+            CHECK_LAUNCH();
+        }
+    }
+    if (depth_out)
+        for (size_t i = 0; i < B; ++i) depth_out[i] = 1;
+    return 0;
+}
+
+extern "C" int exacto_dbfv_plain_mul_sum(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* cts,
+                                         size_t K, size_t polys, const uint64_t* pts, size_t pt_batch, uint64_t* out,
+                                         size_t B, const uint32_t* depth_ct, uint32_t* depth_out) {
+    if (int e = dbfv_plain_mul_check(c, d, base, plain, cts, K, polys, pts, pt_batch, out, B, depth_ct, false)) return e;
+    if (B == 0) return 0;
+    const size_t lb = polys * c->L * poly_bytes(c);
+    return host_call(c, {{cts, B * K * d * lb}, {pts, pt_batch * K * d * poly_bytes(c)}}, B * d * lb, out,
+                     [&](std::vector<u64*>& in, u64* o) {
+                         return exacto_dbfv_plain_mul_sum_dev(c, d, base, plain, in[0], K, polys, in[1], pt_batch, o, B,
+                                                              depth_ct, depth_out);
+                     });
+}
+
+extern "C" int exacto_dbfv_plain_mul_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* ct,
+                                         size_t polys, const uint64_t* pt, size_t pt_batch, uint64_t* out, size_t B,
+                                         const uint32_t* depth_ct, uint32_t* depth_out) {
+    return exacto_dbfv_plain_mul_sum_dev(c, d, base, plain, ct, 1, polys, pt, pt_batch, out, B, depth_ct, depth_out);
+}
+extern "C" int exacto_dbfv_plain_mul(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* ct,
+                                     size_t polys, const uint64_t* pt, size_t pt_batch, uint64_t* out, size_t B,
+                                     const uint32_t* depth_ct, uint32_t* depth_out) {
+    return exacto_dbfv_plain_mul_sum(c, d, base, plain, ct, 1, polys, pt, pt_batch, out, B, depth_ct, depth_out);
+}
+
+// Limb k of the output is bfv_plain_add (eval.rs:489-503) of limb k and plaintext digit k: c0 +- NTT(Delta m)
+static int dbfv_plain_addsub_check(exacto_ctx* c, size_t d, const uint64_t* ct, size_t polys, const uint64_t* pt,
+                                   size_t pt_batch, const uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (!ct || !pt || !out) return invalid_param("null argument");
+    if (polys == 0) return invalid_param("ciphertext has no components");
+    if (pt_batch != 1 && pt_batch != B) return invalid_param("plaintext batch must be 1 or the batch");
+    if (d < 1) return invalid_param("num_digits must be >= 1");
+    if (B > (size_t)INT32_MAX / d) return invalid_param("batch * num_digits too large");
+    return 0;
+}
+static int dbfv_plain_addsub_dev(exacto_ctx* c, bool sub, size_t d, const uint64_t* ct, size_t polys,
+                                 const uint64_t* pt, size_t pt_batch, uint64_t* out, size_t B) {
+    if (int e = dbfv_plain_addsub_check(c, d, ct, polys, pt, pt_batch, out, B)) return e;
+    if (B == 0) return 0;
+    if (int e = lift_plain(c, pt, (long)(pt_batch * d), true)) return e;
+    const long Ln = (long)c->L * c->n;
+    launch_plain_apply(sub ? PLAIN_SUB : PLAIN_ADD, ct, (long)polys * Ln, out, (long)(B * d), (int)polys, c->pl_buf, Ln,
+                       c->n, c->L, c->d_primes, c->stream, pt_batch == B ? 0 : (long)d);
+    CHECK_LAUNCH();
+    return 0;
+}
+static int dbfv_plain_addsub_host(exacto_ctx* c, bool sub, size_t d, const uint64_t* ct, size_t polys,
+                                  const uint64_t* pt, size_t pt_batch, uint64_t* out, size_t B) {
+    if (int e = dbfv_plain_addsub_check(c, d, ct, polys, pt, pt_batch, out, B)) return e;
+    if (B == 0) return 0;
+    const size_t bytes = B * d * polys * c->L * poly_bytes(c);
+    return host_call(c, {{ct, bytes}, {pt, pt_batch * d * poly_bytes(c)}}, bytes, out,
+                     [&](std::vector<u64*>& in, u64* o) {
+                         return dbfv_plain_addsub_dev(c, sub, d, in[0], polys, in[1], pt_batch, o, B);
+                     });
+}
+extern "C" int exacto_dbfv_plain_add_dev(exacto_ctx* c, size_t d, const uint64_t* ct, size_t polys, const uint64_t* pt,
+                                         size_t pt_batch, uint64_t* out, size_t B) {
+    return dbfv_plain_addsub_dev(c, false, d, ct, polys, pt, pt_batch, out, B);
+}
+extern "C" int exacto_dbfv_plain_sub_dev(exacto_ctx* c, size_t d, const uint64_t* ct, size_t polys, const uint64_t* pt,
+                                         size_t pt_batch, uint64_t* out, size_t B) {
+    return dbfv_plain_addsub_dev(c, true, d, ct, polys, pt, pt_batch, out, B);
+}
+extern "C" int exacto_dbfv_plain_add(exacto_ctx* c, size_t d, const uint64_t* ct, size_t polys, const uint64_t* pt,
+                                     size_t pt_batch, uint64_t* out, size_t B) {
+    return dbfv_plain_addsub_host(c, false, d, ct, polys, pt, pt_batch, out, B);
+}
+extern "C" int exacto_dbfv_plain_sub(exacto_ctx* c, size_t d, const uint64_t* ct, size_t polys, const uint64_t* pt,
+                                     size_t pt_batch, uint64_t* out, size_t B) {
+    return dbfv_plain_addsub_host(c, true, d, ct, polys, pt, pt_batch, out, B);
 }
 
 // ============================================================== diagnostics

@@ -371,10 +371,39 @@ void launch_dbfv_linmap(const u64* in, u64* out, const LinTerm* terms, int E, in
 void launch_group_sum(const u64* in, u64* out, const int* slot_start, int groups, int nslots, long items, int n, int L,
                       const PrimeConst* primes, hipStream_t s);
 
+// ---- products of dBFV ciphertexts with plaintext digit vectors (dbfv_plain.hip) ----
+#define DP_MAX_D 8   // the registers form's digit counts; more digits run the list form
+// The list form's pairs: output limb by output limb, pt digit pi times ct digit ci with the coefficient
+// s mod q_l (1 for i + j below d, a fold digit above; 0: nothing to add), last = 1 on a limb's final pair.
+struct DpPair {
+    u64 s;
+    int ci, pi, last, pad_;
+};
+struct DbfvPlainArgs {
+    const u64* cts;              // [items][K][d][polys][L][n], strides in words
+    long ct_item_stride, ct_term_stride;
+    const u64* pl;               // lifted plaintexts [pt items][K][d][L][n]; item stride 0: shared by every item
+    long pl_item_stride, pl_term_stride;
+    u64* out;                    // [items][d][polys][L][n]
+    long items;
+    int K, d, polys, n, L;
+    int flush;                   // products one accumulator takes between two reductions (dbfv_plain.hip)
+    int accum;                   // out += instead of out =
+    unsigned live;               // d <= DP_MAX_D: bit m - d set when wide limb m >= d has a non-zero representative
+    const u64* fold;             // d <= DP_MAX_D and live: [L][d - 1][d], rep[m - d][i] mod q_l
+    const DpPair* pairs;         // d > DP_MAX_D: [E][L]
+    int E;
+    const PrimeConst* primes;
+};
+// every buffer 16-byte aligned, out disjoint from the inputs
+void launch_dbfv_plain_mul(const DbfvPlainArgs& a, hipStream_t s);
+
 // ---- plaintext-ciphertext operations (plain.hip) ----
-enum { PLAIN_MUL = 0, PLAIN_ADD = 1 };
+enum { PLAIN_MUL = 0, PLAIN_ADD = 1, PLAIN_SUB = 2 };
+// pt_period > 0: item i reads plaintext i % pt_period (dBFV limbs against one shared digit vector)
 void launch_plain_apply(int op, const u64* x, long x_item_stride, u64* out, long items, int polys, const u64* pt,
-                        long pt_item_stride, int n, int L, const PrimeConst* primes, hipStream_t s);
+                        long pt_item_stride, int n, int L, const PrimeConst* primes, hipStream_t s,
+                        long pt_period = 0);
 void launch_inner_product(const u64* cts, const u64* pts, u64* out, int K, int polys, int n, int L,
                           const PrimeConst* primes, hipStream_t s);
 void launch_monomials(u64* out, long J, u64 j0, bool neg, int n, int L, const PrimeConst* primes, hipStream_t s);

@@ -18,10 +18,12 @@ static constexpr int PL_TPB = 256;
 // rows [item][poly][limb][n] (x items x_item_stride apart, 0 = one ciphertext for every item);
 // plaintext rows [item (or 0 when pt_item_stride == 0)][limb][n]
 //   op PLAIN_MUL: out = x * pt      (every poly)
-//   op PLAIN_ADD: out = x + pt on poly 0, x elsewhere
+//   op PLAIN_ADD: out = x + pt on poly 0, x elsewhere (PLAIN_SUB: x - pt)
+// pt_period > 0: item i reads plaintext row i % pt_period
 __global__ void __launch_bounds__(PL_TPB)
 plain_apply_kernel(int op, const u64* __restrict__ x, long x_item_stride, u64* __restrict__ out, int polys,
-                   const u64* __restrict__ pt, long pt_item_stride, int n, int L, const PrimeConst* __restrict__ primes) {
+                   const u64* __restrict__ pt, long pt_item_stride, int n, int L, const PrimeConst* __restrict__ primes,
+                   long pt_period) {
     const int nblk = (n + PL_TPB - 1) / PL_TPB;
     const long row = blockIdx.x / nblk;
     const int j = (blockIdx.x - row * nblk) * PL_TPB + threadIdx.x;
@@ -34,19 +36,20 @@ plain_apply_kernel(int op, const u64* __restrict__ x, long x_item_stride, u64* _
     const PrimeConst& P = primes[i];
     const long idx = row * n + j;
     const u64 v = x[item * x_item_stride + r * n + j];
-    const u64 m = pt[item * pt_item_stride + (long)i * n + j];
+    const u64 m = pt[(pt_period ? item % pt_period : item) * pt_item_stride + (long)i * n + j];
     u64 res;
     if (op == PLAIN_MUL) res = mul_mod(v, m, P);
-    else res = poly == 0 ? add_mod(v, m, P.q) : v;
+    else if (op == PLAIN_ADD) res = poly == 0 ? add_mod(v, m, P.q) : v;
+    else res = poly == 0 ? sub_mod(v, m, P.q) : v;
     out[idx] = res;
 }
 
 void launch_plain_apply(int op, const u64* x, long x_item_stride, u64* out, long items, int polys, const u64* pt,
-                        long pt_item_stride, int n, int L, const PrimeConst* primes, hipStream_t s) {
+                        long pt_item_stride, int n, int L, const PrimeConst* primes, hipStream_t s, long pt_period) {
     const long blocks = items * polys * L * ((n + PL_TPB - 1) / PL_TPB);
     if (blocks == 0) return;
     EXACTO_LAUNCH(plain_apply_kernel, dim3((unsigned)blocks), dim3(PL_TPB), 0, s, op, x, x_item_stride, out, polys,
-                       pt, pt_item_stride, n, L, primes);
+                       pt, pt_item_stride, n, L, primes, pt_period);
 }
 
 // out[poly][limb][j] = sum_k cts[k][poly][limb][j] * pts[k][limb][j]  (accumulated in the

@@ -1461,6 +1461,68 @@ inline DbfvCiphertext dbfv_swap_rows(const DbfvCiphertext& ct, const GaloisKey& 
     return dbfv_apply_automorphism(ct, gk);
 }
 
+// ---- dBFV plaintext products (exacto_dbfv_plain_*, no reference function): a public digit vector (d plaintext
+// polynomials, e.g. dbfv_batch_encode's) applied to dBFV ciphertexts: bfv_plain_mul per digit pair, bfv_add by
+// i + j and over the terms, reduce, in one kernel.  A product raises mul_depth as dbfv_mul does.
+namespace detail {
+inline void append_plain(std::vector<uint64_t>& flat, const DbfvSlotPlain& pt, const DbfvParams& dp) {
+    const size_t n = dp.bfv_params->ring_degree;
+    if (pt.size() != dp.num_digits) throw ExactoError(1, "invalid parameter: expected d digit plaintexts");
+    for (auto& p : pt) {
+        if (p.coeffs.size() != n)
+            throw ExactoError(2, "dimension mismatch: expected " + std::to_string(n) + ", got " +
+                                     std::to_string(p.coeffs.size()));
+        flat.insert(flat.end(), p.coeffs.begin(), p.coeffs.end());
+    }
+}
+}  // namespace detail
+// sum_k pts[k] * cts[k]
+inline DbfvCiphertext dbfv_plain_mul_sum(const std::vector<DbfvCiphertext>& cts, const std::vector<DbfvSlotPlain>& pts) {
+    if (cts.empty() || cts.size() != pts.size()) throw ExactoError(1, "invalid parameter: mismatched ct/pt lengths");
+    const DbfvParams& dp = *cts[0].params;
+    const size_t d = dp.num_digits, polys = detail::dbfv_polys(cts[0]);
+    std::vector<uint64_t> fc, fp;
+    std::vector<uint32_t> depth;
+    for (size_t k = 0; k < cts.size(); ++k) {
+        if (cts[k].num_limbs() != d) throw ExactoError(1, "invalid parameter: multiplication requires d-limb ciphertexts");
+        auto x = detail::flatten(cts[k].limbs, polys);
+        fc.insert(fc.end(), x.begin(), x.end());
+        detail::append_plain(fp, pts[k], dp);
+        depth.push_back((uint32_t)cts[k].mul_depth);
+    }
+    std::vector<uint64_t> out(d * polys * detail::limb_words(dp));
+    uint32_t dout = 0;
+    detail::check(exacto_dbfv_plain_mul_sum(dp.bfv_params->ctx(), d, dp.base, dp.plain_modulus, fc.data(), cts.size(),
+                                            polys, fp.data(), 1, out.data(), 1, depth.data(), &dout));
+    return detail::make_dbfv(out, d, polys, d, dout, cts[0].params);
+}
+inline DbfvCiphertext dbfv_plain_mul(const DbfvCiphertext& ct, const DbfvSlotPlain& pt) {
+    return dbfv_plain_mul_sum(std::vector<DbfvCiphertext>{ct}, std::vector<DbfvSlotPlain>{pt});
+}
+namespace detail {
+inline DbfvCiphertext dbfv_plain_addsub(bool sub, const DbfvCiphertext& ct, const DbfvSlotPlain& pt) {
+    const DbfvParams& dp = *ct.params;
+    const size_t d = ct.num_limbs(), polys = dbfv_polys(ct);
+    if (d != dp.num_digits) throw ExactoError(1, "invalid parameter: expected d-limb dBFV ciphertext");
+    auto f = flatten(ct.limbs, polys);
+    std::vector<uint64_t> fp, out(f.size());
+    append_plain(fp, pt, dp);
+    check((sub ? exacto_dbfv_plain_sub : exacto_dbfv_plain_add)(dp.bfv_params->ctx(), d, f.data(), polys, fp.data(), 1,
+                                                                 out.data(), 1));
+    return make_dbfv(out, d, polys, ct.degree, ct.mul_depth, ct.params);
+}
+}  // namespace detail
+inline DbfvCiphertext dbfv_plain_add(const DbfvCiphertext& ct, const DbfvSlotPlain& pt) {
+    return detail::dbfv_plain_addsub(false, ct, pt);
+}
+inline DbfvCiphertext dbfv_plain_sub(const DbfvCiphertext& ct, const DbfvSlotPlain& pt) {
+    return detail::dbfv_plain_addsub(true, ct, pt);
+}
+// Slot-wise ct * values mod p: dbfv_batch_encode, then dbfv_plain_mul.
+inline DbfvCiphertext dbfv_batch_plain_mul(const DbfvCiphertext& ct, const SlotVector& values) {
+    return dbfv_plain_mul(ct, dbfv_batch_encode(values, ct.params));
+}
+
 // dbfv_div_by_base (src/dbfv/advanced.rs:36-93): the result carries new DbfvParams with p / base.
 inline DbfvCiphertext dbfv_div_by_base(const DbfvCiphertext& ct) {
     const DbfvParams& dp = *ct.params;

@@ -714,6 +714,58 @@ int exacto_dbfv_batch_decrypt(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t
 int exacto_dbfv_batch_decrypt_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
                                   const uint64_t* ct, const uint64_t* sk, uint64_t* values_out, size_t batch);
 
+/* dBFV plaintext products: public wide operands (weights, a matrix row, a constant vector) applied to dBFV
+ * ciphertexts.  No reference function (dbfv/advanced.rs stops at bfv_scalar_plain_mul); the definition is the
+ * composition of bfv_plain_mul (bfv/eval.rs:468-486) per digit pair, bfv_add by i + j and over k, and reduce
+ * (dbfv/reduction.rs:15-93), bit for bit, in one fused kernel (dbfv_plain.hip).
+ *   cts [B][K][d][polys][L][n] (NTT domain, polys >= 1), pts [pt_batch][K][d][n] plaintext coefficients (any
+ *   u64, reduced mod each q_l as exacto_bfv_plain_mul lifts them: what exacto_dbfv_batch_encode writes),
+ *   pt_batch = B or 1 (1: one plaintext for every item), out [B][d][polys][L][n].
+ * With P[k][i] = NTT(pts[k][i] mod q_l) and wide[m] = sum over k and over i + j = m of P[k][i] (.) cts[k][j]
+ * (m = 0 .. 2d-2): out[i] = wide[i] + sum_{m >= d} rep[m-d][i] wide[m], rep = SmallReps::compute_simple(base,
+ * d, p) (lattice.rs:104-122), canonical residues mod q_l.  Pairs whose wide limb has an all-zero
+ * representative are not formed (p = 2^64, b = 256, d = 8: only i + j < d, as in exacto_dbfv_mul_plan).
+ * exacto_dbfv_plain_mul is K = 1.  depth_ct: host [B][K] (NULL = 0); depth_out[b] = max_k depth + 1 (NULL
+ * allowed).  A plaintext product grows the digits as a ciphertext product does: an input depth >= 1 is
+ * exacto_dbfv_mul's NotImplemented error.  The plaintexts are lifted into a context-owned buffer of at
+ * most exacto_ctx_set_plain_terms terms (default 64; 0 restores it) for one plaintext, or for one chunk of
+ * items (exacto_ctx_set_chunk) with plaintexts of their own; a later term chunk adds into out.  Neither
+ * setting changes a result.  A batching context is NOT required: the product is defined for any plaintext
+ * polynomials, and slot semantics is the caller's encoding.
+ * exacto_dbfv_plain_add / _sub: ct [B][d][polys][L][n], pt [pt_batch][d][n] -> out likewise; limb k of the
+ *   output is exacto_bfv_plain_add of limb k and digit k, c0 + NTT(Delta m) (sub: c0 - NTT(Delta m)), the other
+ *   components copied; depth unchanged; out may be ct.
+ * Errors, all before any launch and in this order: the context's; InvalidParam for a null pointer; K == 0
+ * ("mismatched ct/pt lengths"); polys == 0; pt_batch not in {1, B}; those of DbfvParams::new (_add / _sub:
+ * d == 0 only); more than 64 digits; the depth error; a _dev buffer that is not 16-byte aligned (products
+ * only); out overlapping cts or pts (products only).  batch == 0 returns 0.  The _dev forms are asynchronous
+ * on the context's stream.
+ * exacto_dbfv_plain_limits: what a test needs to cross both chunkings: the products one 128-bit accumulator of
+ * the kernel takes between two reductions (2^(128 - 2 s) - 2 for the largest prime's bit length s, at most
+ * 2^20; the registers form, d <= 8, reduces every flush_products / d terms) and the term chunk. */
+int exacto_dbfv_plain_mul_sum(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                              const uint64_t* cts, size_t K, size_t polys, const uint64_t* pts, size_t pt_batch,
+                              uint64_t* out, size_t batch, const uint32_t* depth_ct, uint32_t* depth_out);
+int exacto_dbfv_plain_mul_sum_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                                  const uint64_t* cts, size_t K, size_t polys, const uint64_t* pts, size_t pt_batch,
+                                  uint64_t* out, size_t batch, const uint32_t* depth_ct, uint32_t* depth_out);
+int exacto_dbfv_plain_mul(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus, const uint64_t* ct,
+                          size_t polys, const uint64_t* pt, size_t pt_batch, uint64_t* out, size_t batch,
+                          const uint32_t* depth_ct, uint32_t* depth_out);
+int exacto_dbfv_plain_mul_dev(exacto_ctx* ctx, size_t d, uint64_t base, uint64_t dbfv_plain_modulus,
+                              const uint64_t* ct, size_t polys, const uint64_t* pt, size_t pt_batch, uint64_t* out,
+                              size_t batch, const uint32_t* depth_ct, uint32_t* depth_out);
+int exacto_dbfv_plain_add(exacto_ctx* ctx, size_t d, const uint64_t* ct, size_t polys, const uint64_t* pt,
+                          size_t pt_batch, uint64_t* out, size_t batch);
+int exacto_dbfv_plain_add_dev(exacto_ctx* ctx, size_t d, const uint64_t* ct, size_t polys, const uint64_t* pt,
+                              size_t pt_batch, uint64_t* out, size_t batch);
+int exacto_dbfv_plain_sub(exacto_ctx* ctx, size_t d, const uint64_t* ct, size_t polys, const uint64_t* pt,
+                          size_t pt_batch, uint64_t* out, size_t batch);
+int exacto_dbfv_plain_sub_dev(exacto_ctx* ctx, size_t d, const uint64_t* ct, size_t polys, const uint64_t* pt,
+                              size_t pt_batch, uint64_t* out, size_t batch);
+int exacto_ctx_set_plain_terms(exacto_ctx* ctx, size_t terms);
+int exacto_dbfv_plain_limits(exacto_ctx* ctx, size_t* flush_products, size_t* chunk_terms);
+
 /* Plaintext-ciphertext operations (CoeffsToSlots' linear layer), all in the NTT domain.
  * ct/out [B][polys][L][n]; pt [B][n] plaintext coefficients (any u64, reduced mod each q_i).
  *   bfv_plain_mul     replaces bfv::eval::bfv_plain_mul      (src/bfv/eval.rs:468-486)
