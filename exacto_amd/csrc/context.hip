@@ -4,28 +4,8 @@
 // the selected multiplication path), per-prime NTT twiddle tables and constants in
 // HBM, the exact-CRT tables, the resident relinearisation key and a chunked
 // workspace.  Every `_dev` entry point only enqueues kernels on the context stream.
-#include <algorithm>
-#include <array>
-#include <cxxabi.h>
-#include <dlfcn.h>
-#include <chrono>
-#include <condition_variable>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <functional>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <set>
-#include <string>
-#include <thread>
-#include <type_traits>
-#include <vector>
 
-#include "../../include/exacto_hip.h"
-#include "exacto_internal.hpp"
+#include "runtime.hpp"
 
 using namespace exacto;
 
@@ -35,26 +15,11 @@ thread_local const void* exacto::g_last_kernel = nullptr;
 
 static thread_local std::string g_last_error;
 
-static int fail(int code, const std::string& msg) {
+int exacto::fail(int code, const std::string& msg) {
     g_last_error = msg;
     return code;
 }
-static int invalid_param(const std::string& s) { return fail(EXACTO_ERR_INVALID_PARAM, "invalid parameter: " + s); }
-
-#define HIP_TRY(x)                                                                              \
-    do {                                                                                        \
-        hipError_t e_ = (x);                                                                    \
-        if (e_ != hipSuccess)                                                                   \
-            return fail(EXACTO_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(e_) +    \
-                                            " (" #x ")");                                       \
-    } while (0)
-
-#define CHECK_LAUNCH()                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = hipGetLastError();                                                      \
-        if (e_ != hipSuccess)                                                                   \
-            return fail(EXACTO_ERR_HIP, std::string("HIP launch error: ") + hipGetErrorString(e_)); \
-    } while (0)
+int exacto::invalid_param(const std::string& s) { return fail(EXACTO_ERR_INVALID_PARAM, "invalid parameter: " + s); }
 
 // ============================================================== host integer helpers
 
@@ -93,7 +58,7 @@ static bool is_prime_h(u64 n) {
 }
 
 // modular inverse via extended Euclid (returns 0 if not invertible)
-static u64 invmod_h(u64 a, u64 m) {
+u64 exacto::invmod_h(u64 a, u64 m) {
     i128 t = 0, nt = 1, r = m, nr = a % m;
     while (nr != 0) {
         i128 q = r / nr;
@@ -105,7 +70,7 @@ static u64 invmod_h(u64 a, u64 m) {
     return (u64)t;
 }
 
-static u64 shoup_h(u64 w, u64 q) { return (u64)(((u128)w << 64) / q); }
+u64 exacto::shoup_h(u64 w, u64 q) { return (u64)(((u128)w << 64) / q); }
 static int bitlen(u64 x) { return x ? 64 - __builtin_clzll(x) : 0; }
 
 static int bitrev(int x, int bits) {
@@ -123,48 +88,6 @@ static u64 find_psi(u64 n, u64 q) {
     }
 }
 
-// --- minimal unsigned big integer (little-endian 64-bit words) ---
-struct Big {
-    std::vector<u64> w;
-    Big(u64 v = 0) { w.push_back(v); trim(); }
-    void trim() { while (w.size() > 1 && w.back() == 0) w.pop_back(); }
-    void mul(u64 m) {
-        u64 c = 0;
-        for (auto& x : w) { u128 t = (u128)x * m + c; x = (u64)t; c = (u64)(t >> 64); }
-        if (c) w.push_back(c);
-        trim();
-    }
-    void add(u64 a) {
-        for (size_t i = 0; i < w.size() && a; ++i) { u64 s = w[i] + a; a = s < a; w[i] = s; }
-        if (a) w.push_back(a);
-    }
-    void add(const Big& o) {
-        u64 carry = 0;
-        for (size_t i = 0; i < std::max(w.size(), o.w.size()) || carry; ++i) {
-            if (i == w.size()) w.push_back(0);
-            const u128 t = (u128)w[i] + (i < o.w.size() ? o.w[i] : 0) + carry;
-            w[i] = (u64)t;
-            carry = (u64)(t >> 64);
-        }
-        trim();
-    }
-    void shr1() {
-        for (size_t i = 0; i < w.size(); ++i) w[i] = (w[i] >> 1) | (i + 1 < w.size() ? w[i + 1] << 63 : 0);
-        trim();
-    }
-    u64 mod(u64 m) const {
-        u128 r = 0;
-        for (size_t i = w.size(); i-- > 0;) r = ((r << 64) | w[i]) % m;
-        return (u64)r;
-    }
-    int cmp(const Big& o) const {
-        if (w.size() != o.w.size()) return w.size() < o.w.size() ? -1 : 1;
-        for (size_t i = w.size(); i-- > 0;)
-            if (w[i] != o.w[i]) return w[i] < o.w[i] ? -1 : 1;
-        return 0;
-    }
-};
-
 // mixed-radix digits of X (given as residues mod primes[0..cnt)) — host Garner
 static std::vector<u64> mixed_radix(const std::vector<u64>& res, const std::vector<u64>& pr) {
     std::vector<u64> v(pr.size());
@@ -179,293 +102,6 @@ static std::vector<u64> mixed_radix(const std::vector<u64>& res, const std::vect
     }
     return v;
 }
-
-// ============================================================== context
-
-struct ProfRec {
-    int kind;
-    hipEvent_t a, b;
-    u64 polys;
-    double bytes;
-    const void* kern;   // host handle of the last kernel launched inside the scope (EXACTO_LAUNCH)
-};
-
-static void free_dev(void* p);
-static hipError_t dev_alloc(void** p, size_t bytes);
-
-// A device buffer that owns its memory.  Move-only; released through free_dev when its owner goes, so
-// every release reaches the EXACTO_DEBUG_ALLOC log.  It converts to its pointer, so the launchers take
-// it as they took the raw pointer; nothing outside the type assigns the pointer or the capacity.
-template <class T>
-class DevBuf {
-    T* p_ = nullptr;
-    size_t cap_ = 0;   // bytes
-public:
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        if (this != &o) {
-            reset();
-            p_ = o.p_; cap_ = o.cap_;
-            o.p_ = nullptr; o.cap_ = 0;
-        }
-        return *this;
-    }
-    ~DevBuf() { reset(); }
-    operator T*() const { return p_; }
-    T* get() const { return p_; }
-    size_t bytes() const { return cap_; }
-    void reset() {
-        free_dev(p_);
-        p_ = nullptr;
-        cap_ = 0;
-    }
-    // exactly `bytes` (the tables allocated once, the workspaces): what it held is released first
-    int alloc(size_t bytes) {
-        reset();
-        HIP_TRY(dev_alloc((void**)&p_, bytes));
-        cap_ = bytes;
-        return 0;
-    }
-    // at least max(bytes, 8): nothing when the capacity suffices, else free first, then allocate (the
-    // old and the new block are never live together).  A failure leaves the buffer empty.
-    int grow(size_t bytes) {
-        bytes = std::max<size_t>(bytes, 8);
-        return cap_ >= bytes ? 0 : alloc(bytes);
-    }
-};
-static_assert(!std::is_copy_constructible<DevBuf<u64>>::value && !std::is_copy_assignable<DevBuf<u64>>::value,
-              "a device buffer has one owner");
-
-// A 31-bit auxiliary basis of the ks32 key switch (ks32.hip) with its device tables and the
-// relinearisation key converted to it.
-struct Ks32Basis {
-    int S = 0;
-    int sum_max = 0;              // dBFV key-switch sums the basis lifts exactly
-    int fpc_max = 0;              // ... and by the float-CRT lift (ks32_fpc_one's margin; S <= 3 or p < 2^32 / 3)
-    int mac_form = 0;             // ks32_mac: 0 primes up to 2^31 (7 products per reduction),
-                                  // 1 below 2^32 / 3 (12), 2 below 2^30 (12, lazy transforms)
-    Big P;                        // product of the primes
-    DevBuf<Prime32> d_p32;
-    DevBuf<uint2> d_tw32;
-    DevBuf<Ks32Tables> d_kst;
-    DevBuf<uint32_t> d_rs;        // the relinearisation key in this basis
-    bool rs_valid = false;
-};
-static_assert(!std::is_copy_constructible<Ks32Basis>::value && !std::is_copy_assignable<Ks32Basis>::value,
-              "a basis owns its tables");
-
-// The per-chunk workspace of one pipeline lane, sized in items (products) by ensure().
-struct exacto_ctx;
-struct Workspace {
-    size_t items = 0;
-    DevBuf<u64> coefQ, extP, T, D;
-    // exact path with gadget base <= 2^16: the scale kernel writes each digit once as int16 and
-    // the digit NTT converts it per limb on load (EXACTO_DIGIT16=0: u64 digits per limb)
-    DevBuf<int16_t> D16;
-    DevBuf<uint32_t> DS, U;   // ks32: digit residues [item][G][S][n] and accumulators [item][2L][S][n]
-    int ensure(const exacto_ctx* c, size_t want);
-};
-
-// Stream and per-chunk workspace of one extra pipeline lane (lane 0 is the context's own).
-constexpr int EXACTO_MAX_LANES = 4;
-struct LaneSet {
-    hipStream_t stream = nullptr;
-    hipEvent_t join = nullptr;
-    Workspace ws;
-};
-
-struct exacto_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int n = 0, logn = 0, L = 0, K = 0;
-    std::vector<u64> ctq, user_aux, int_aux, primes;  // primes = ctq ++ (path aux)
-    u64 plain = 0, gbase = 0;
-    int G = 0;
-    int path = EXACTO_PATH_EXACT_RNS;
-    int deferred_code = 0;  // error raised at multiplication time (reference semantics)
-    std::string deferred_msg;
-    DevBuf<PrimeConst> d_primes;
-    DevBuf<TwPair> d_tw;
-    DevBuf<CrtTables> d_crt;
-    CrtTables h_crt{};
-    DevBuf<u64> d_scal;
-    DevBuf<u64> d_rlk;
-    DevBuf<u64> d_rlk_s;  // Shoup companions of the key (limb-wise relinearisation MAC)
-    size_t rlk_keys = 0;
-    bool rlk_s_valid = false;
-    // EXACTO_NTT_ASM=0: no special-prime (2^60 - d) asm rounds; those batches then take the generated
-    // generic-prime asm rounds where their size has them (n = 1024 / 4096 / 8192, lazy primes), and the
-    // compiler-scheduled C++ rounds only with EXACTO_NTT_GEN=0 as well (A/B switches)
-    bool ntt_asm = true;
-    bool ntt_asm_inv = true;  // EXACTO_NTT_ASM_INV=0: compiler-scheduled inverse NTT (A/B)
-    // relinearisation MAC in an auxiliary basis of S 31-bit primes (ks32.hip; EXACTO_KS32=0: the
-    // limb-wise 60-bit digit NTTs + relin_mac)
-    bool ks32 = true;
-    int S32 = 0;                 // 0: not eligible for these parameters
-    int ks32_sum_max = 0;        // key-switch sums that may be added before one lift (prod p bound)
-    int ks32_fpc_max = 0;        // ... that the active basis' float-CRT lift takes (Ks32Basis::fpc_max)
-    bool ks_fpc = true;          // EXACTO_KS_FPC=0: the Garner lift in ks32_crt always (A/B)
-    int ks32_mac_form = 0;       // ks32_mac's reduction form for the active basis (Ks32Basis::mac_form)
-    Ks32Basis kw;                // wide basis (primes up to 2^31) for dBFV digit sums the primary cannot hold
-    // The primary basis is one of two, chosen per relinearisation key (ensure_rs):
-    //   kn: narrow primes below 2^32 / 3 bounding |sum_g d_g * r_g| by G n ceil(B/2) (q/2) for ANY key;
-    //   kz: lazy primes below 2^30 (cheaper 32-bit butterflies, ks32_dev.hpp), used when the resident
-    //       key's own L1 norms bound the sum: |u_{c,l}| <= ceil(B/2) sum_g ||r_{g,c,l}||_1 < prod p / 2
-    //       (a uniform key has ||r||_1 ~ n q / 4: half the generic bound).  EXACTO_KS32_LAZY=0: kn only.
-    // S32 / d_p32 / d_tw32 / d_kst / ks32_sum_max / ks32_mac_form describe the active one.
-    Ks32Basis kn, kz;
-    bool ks32_lazy_active = false;
-    int ks32_need_m = 1;          // the most key-switch sums per output limb a dbfv_mul of this context asked for
-    int last_dbfv_ks = -1;        // exacto_ctx_info.dbfv_key_switch
-    int last_mul_sum_mode = -1;   // exacto_bfv_mul_sum_info: the same codes for the last bfv_mul_sum
-    size_t mul_sum_cap = 0;       // exacto_ctx_set_mul_sum_group (0: the context's own limit)
-    // a dBFV pass with shared extensions: d and its products per item (0: plain BFV products), for
-    // run_inv_tensor's algorithmic bytes and the tensor kernels' prime-major block order
-    int tensor_share_d = 0, tensor_share_npairs = 0;
-    // dBFV chain: the step that formed the output limbs in the coefficient domain also lifted them to
-    // the auxiliary primes into ext_a and transformed both in one launch; the next step's extension of
-    // its left operand is then already in ext_a (measured A/B: DESIGN.md §6.4)
-    bool ext_a_ready = false;
-    // (a view of d_dall, not owned) run_mul: int16 digits of product p to ks_defer + p G n, no key switch
-    int16_t* ks_defer = nullptr;
-    bool ks_defer8 = false;       // ... int8 digits instead (base <= 2^8; EXACTO_DIGIT8=0: int16)
-    bool digit8_env = true;
-    // dBFV psum (EXACTO_PSUM=0: off): an output limb's c0 / c1 scaled once from the sum of its
-    // products' tensors in the auxiliary primes (run_mul, dbfv_mul_core); psum_max = the largest
-    // product count m with m (p n Q + 2) < P, so that the summed rounding stays liftable from P
-    bool psum_env = true;
-    bool square_hook = true;     // eval_poly's baby steps x^(i/2) x^(i/2) on the square path (exacto_ctx_set_square_hook)
-    int psum_max = 0;
-    int psum_fp_max = 0;         // ... and with |sum| < P / 4, the rounded-float CRT over P (kernels.hip fpc_lift)
-    bool fp_crt = true;          // EXACTO_FP_CRT=0: Garner over P in the SP scale kernels (A/B)
-    // the scale kernels' s = [p T]_Q by a rounded float sum (with fp_crt; kernels.hip fpq_y) wherever
-    // |f - round(f)| <= fpq_lim.  EXACTO_FPQ=0: Garner over Q always; =2: a 1/4 band (half the
-    // coefficients take Garner: the fallback's bit-exact variant)
-    double fpq_lim = 0.5 - 0x1p-40;
-    // HPS: the division-free scale (q > 2^32, p < min(q, 2^32); EXACTO_HPS_LITERAL=1: the literal i128
-    // form, kept for the equivalence test) and, in dbfv_mul, the products' c0 / c1 and signed gadget
-    // digits summed per output limb before ONE forward NTT + relinearisation MAC per limb
-    // (EXACTO_HPS_SUM=0: per product)
-    bool hps_fast = false;
-    bool hps_sum_env = true;
-    struct PsumPlan {
-        bool on = false;
-        int d = 0, npairs = 0;
-        const int* term_start = nullptr;
-        const CombineTerm* terms = nullptr;
-        u64* out = nullptr;       // [B][d][2][L][n], coefficient domain (a view: the caller's buffer)
-        bool fpc = false;         // its scale may take the rounded-float CRT over P (m <= psum_fp_max)
-    } psum;
-    DevBuf<u64> d_hdig;          // dBFV over HPS: the summed digits' NTT residues [B][d][G][L][n]
-    DevBuf<int16_t> d_dall;      // dBFV: per-product digits
-    DevBuf<void> d_dk;           // ... and their per-limb sums (int16, or int32 when m ceil(B/2) > 2^15 - 1)
-    DevBuf<uint32_t> d_dsk, d_uk;   // their residues and key-switch sums in the 31-bit basis
-    // views of the active basis' tables (use_ks32_basis): kn / kz own them
-    Prime32* d_p32 = nullptr;
-    uint2* d_tw32 = nullptr;
-    Ks32Tables* d_kst = nullptr;
-    DevBuf<uint32_t> d_rs;       // key in the auxiliary basis [keys][2L][S][n], NTT domain mod p_s
-    bool rs_valid = false;
-    bool rlk_loaded = false;
-    // workspace (per chunk) of lane 0
-    size_t chunk = 512;  // products per pipeline pass; throughput plateaus from ~512 (r1 sweep)
-    Workspace ws;
-    bool digit16 = true;   // EXACTO_DIGIT16=0: u64 digits per limb instead of Workspace::D16
-    // further pipeline lanes: chunk i runs on lane i % lanes, each lane a stream with its own
-    // workspace, so the kernels of consecutive chunks overlap (EXACTO_DUAL_STREAM=0: one lane;
-    // EXACTO_LANES: lane count, 2 by default)
-    bool dual = true;
-    int lanes = 2;
-    hipEvent_t ev_fork = nullptr;
-    // dBFV chains of two or more items run as two halves on two streams (exacto_dbfv_mul_chain_dev):
-    // the second half on a twin context (same parameters, its own stream and workspaces, a copy of
-    // the relinearisation key), so each half's whole chain overlaps the other's
-    static constexpr int MAX_TWINS = 3;
-    exacto_ctx* twin[MAX_TWINS] = {};
-    bool batch_split = true;         // EXACTO_CHAIN_SPLIT=0: one stream for the whole batch
-    unsigned rlk_version = 0, twin_rlk_version[MAX_TWINS] = {~0u, ~0u, ~0u};
-    hipEvent_t ev_twin_in = nullptr, ev_twin_out[MAX_TWINS] = {};
-    LaneSet xl[EXACTO_MAX_LANES - 1];   // lanes 1 .. lanes-1
-    // dBFV: per-ciphertext extensions shared by the products that use the ciphertext
-    // (EXACTO_SHARE_EXT=0 recomputes them per product)
-    bool share_ext = true;
-    // keygen / encryption
-    DevBuf<double> d_cdt;
-    double cdt_sigma = 0.0;
-    DevBuf<u64> d_gpow;
-    DevBuf<u64> d_delta;
-    bool delta_ok = false;
-    DevBuf<u64> enc_buf;
-    DevBuf<u64> d_lin;  // terms of the last dBFV linear map, LinTerm [E][L]
-    std::vector<u64> lin_host;  // what d_lin holds
-    DevBuf<u64> d_dp;   // fold digits or pair list of the last dBFV plaintext product (dbfv_plain_tables)
-    std::vector<u64> dp_host;   // what d_dp holds
-    size_t plain_terms = 64;    // dBFV plaintext products: terms lifted into pl_buf at a time
-    DevBuf<u64> gk_s;  // Shoup companions of the Galois key of the last automorphism call
-    DevBuf<uint32_t> d_gk_rs;  // ks32: Galois key of the last automorphism call in the 31-bit basis
-    DevBuf<u64> pl_buf;  // lifted plaintexts / monomial scratch
-    DevBuf<u64> ext_a, ext_b;
-    DevBuf<u64> chain_buf;  // dBFV chain ping-pong buffers
-    // dBFV chain, psum path: each step's relinearised limbs also in the coefficient domain (they are
-    // there before the final forward NTT), so the next step's extension lifts them directly instead
-    // of inverse-transforming its NTT-domain input (dbfv_mul_group, exacto_dbfv_mul_chain_dev)
-    DevBuf<u64> chain_coef;
-    // (coef_out and coef_in are views into chain_coef halves, not owned)
-    u64* coef_out = nullptr;        // where this step's coefficient form went (psum steps of a chain)
-    int coef_slot = -1;             // set by the chain: chain_coef half for this step's coefficient form
-    size_t coef_slot_words = 0;     // ... and the size of one half
-    const u64* coef_in = nullptr;   // set by the chain: the coefficient form of this step's `a`
-    bool coef_written = false;      // reported back: coef_out holds this step's results
-    DevBuf<u64> dec_buf;    // decryption phase [B][L][n]
-    DevBuf<u64> dig_buf;    // dBFV decrypted digits [B][d][n]
-    // staging for host-pointer API and dBFV products
-    DevBuf<u64> io;
-    DevBuf<u64> prod;
-    // product-sum plan cache (dbfv_mul's index rule, or bfv_mul_sum's term lists: cached_kind)
-    DevBuf<u64> d_off;
-    int cached_kind = -1;            // 0: dbfv_plan, 1: mul_sum_plan, 2: dbfv_plan's symmetric form; -1: none
-    std::vector<uint32_t> cached_ms; // mul_sum_plan: ia, ib, slot lists, then na, nb, nslots, group limit
-    int cached_ngroups = 0;          // mul_sum_plan: groups of the cached plan (its "output limbs")
-    DevBuf<int> d_slot_start;        // ... and, when a slot has several, slot s = groups [start[s], start[s+1])
-    DevBuf<u64> gsum_buf;            // bfv_mul_sum: the groups' coefficient-domain results [B][groups][2][L][n]
-    // modulus switch: q_j^-1 mod q_i (j > i) at [j * L + i] with their Shoup companions, built on first use;
-    // the intermediate levels of a call that drops several primes (two halves, one chunk each)
-    std::vector<u64> msw_w, msw_ws;
-    DevBuf<u64> msw_buf;
-    // SIMD batching (batch.hip): validated and built at the context's first batching call (batch_ready)
-    int batch_state = 0;             // 0: not tried, 1: tables resident, -1: this context cannot batch
-    int batch_code = 0;              // ... and why
-    std::string batch_msg;
-    u64 batch_root = 0;              // zeta = find_psi(n, t)
-    int batch_form = 0;              // the transforms' arithmetic (F32_LAZY / F32_WIDE / BF_STRICT)
-    BatchTab batch_tab{};
-    DevBuf<uint2> d_btw;             // [2][n] forward, inverse twiddles mod t
-    DevBuf<uint32_t> d_bperm;        // [n] slot -> storage position
-    DevBuf<u64> batch_buf;           // the compositions' plaintexts, one chunk
-    size_t cached_B = 0, cached_d = 0;
-    u64 cached_base = 0, cached_p = 0;
-    int cached_npairs = 0;
-    std::vector<int> cached_limbs;   // output limbs of the cached plan (all d, or a subset: exacto_dbfv_mul_limbs)
-    int cached_sum_m = 0;        // max products per dBFV output limb when all combine terms are sums, else -1
-    DevBuf<int> d_term_start;
-    DevBuf<CombineTerm> d_terms;
-    // per-call scratch: the context's own stream-ordered pool (Scratch)
-    hipMemPool_t pool = nullptr;
-    // the bootstrap's intermediates (coefficients, flags, the c0'/c1' rows, phase, slots): a persistent
-    // buffer of the boot context, grown like the workspaces, never from the stream-ordered pool
-    DevBuf<u64> boot_buf;
-    DevBuf<u64> boot_slots;      // ... and the slots of the ring path, grown when an item takes it
-    bool debug_scratch = false;
-    size_t dbfv_group_bytes = (size_t)16384 << 20;  // dbfv_mul item groups (EXACTO_DBFV_GROUP_MB)
-    // profiling
-    bool prof = false;
-    std::vector<ProfRec> recs;
-    std::map<int, std::map<const void*, std::pair<u64, double>>> prof_kern;   // kind -> kernel -> (launches, ms)
-};
 
 // EXACTO_DEBUG_ALLOC=1: every device allocation and release of the library is logged
 // to stderr with its pointer, size, pool and stream; =2 adds the allocation range the runtime reports
@@ -488,7 +124,7 @@ static void dbg_alloc_log(const char* what, const void* p, size_t bytes, const v
                  (void*)base, sz);
 }
 
-static void free_dev(void* p) {
+void exacto::free_dev(void* p) {
     if (p) {
         dbg_alloc_log("hipFree", p, 0, nullptr, nullptr, false);
         (void)hipFree(p);
@@ -531,7 +167,7 @@ struct Scratch {
 // with 0xA5 bytes, so that a kernel reading memory nothing wrote sees garbage at once instead of the
 // zeros of fresh pages (a read of that kind passed in a fresh process and failed after other work
 // had freed and re-used the memory).
-static hipError_t dev_alloc(void** p, size_t bytes) {
+hipError_t exacto::dev_alloc(void** p, size_t bytes) {
     static const bool fill = [] { const char* e = getenv("EXACTO_DEBUG_FILL"); return e && e[0] == '1'; }();
     hipError_t e = hipMalloc(p, bytes);
     if (e == hipSuccess) dbg_alloc_log("hipMalloc", *p, bytes, nullptr, nullptr, true);
@@ -1270,7 +906,7 @@ extern "C" int exacto_synchronize(exacto_ctx* c) {
     return 0;
 }
 
-static size_t poly_bytes(const exacto_ctx* c) { return (size_t)c->n * sizeof(u64); }
+size_t exacto::poly_bytes(const exacto_ctx* c) { return (size_t)c->n * sizeof(u64); }
 
 extern "C" uint64_t* exacto_ctx_relin_key_buffer(exacto_ctx* c, size_t num_keys) {
     if (!c) return nullptr;
@@ -1306,36 +942,7 @@ extern "C" int exacto_ctx_load_relin_key(exacto_ctx* c, const uint64_t* rlk, siz
 
 // ============================================================== NTT helper (+ profiling)
 
-// Kernel families timed by exacto_prof_enable (HIP events around each launch on the launching
-// stream; the bench's roofline takes the family with the largest share of a profiled step).
-// Bytes are ALGORITHMIC: each operand read once and each result written once.
-enum ProfKind : int {
-    PK_FWD = 0, PK_INV = 1, PK_TENSOR = 2, PK_POLYMUL = 3, PK_LIFT = 4, PK_SCALE = 5, PK_KS_DIGITS = 6,
-    PK_KS_MAC = 7, PK_KS_CRT = 8, PK_PAIRSUM = 9, PK_PSUM_SCALE = 10, PK_TENSOR_C2 = 11, PK_DIGIT_SUM = 12,
-    PK_COMBINE = 13, PK_HPS_EXT = 14, PK_RELIN_MAC = 15, PK_HPS_SCALE = 16, PK_GROUP_SUM = 17, PK_MODSWITCH = 18,
-    PK_COUNT = 19
-};
-
-struct ProfScope {
-    exacto_ctx* c;
-    ProfRec rec{};
-    bool on;
-    ProfScope(exacto_ctx* c_, int kind, u64 units, double bytes) : c(c_), on(c_->prof) {
-        if (!on) return;
-        rec.kind = kind; rec.polys = units; rec.bytes = bytes;
-        g_last_kernel = nullptr;
-        if (hipEventCreate(&rec.a) != hipSuccess || hipEventCreate(&rec.b) != hipSuccess ||
-            hipEventRecord(rec.a, c->stream) != hipSuccess)
-            on = false;
-    }
-    ~ProfScope() {
-        if (!on) return;
-        rec.kern = g_last_kernel;
-        if (hipEventRecord(rec.b, c->stream) == hipSuccess) c->recs.push_back(rec);
-    }
-};
-
-static int run_ntt(exacto_ctx* c, const NttBatch& nb, long count, bool inverse) {
+int exacto::run_ntt(exacto_ctx* c, const NttBatch& nb, long count, bool inverse) {
     if (count <= 0) return 0;
     // algorithmic bytes: one read of the source (int16 digits: 2 B per coefficient) + one 8 B write
     ProfScope ps(c, inverse ? PK_INV : PK_FWD, (u64)count, ((nb.src16 ? 2.0 : 8.0) + 8.0) * c->n * (double)count);
@@ -1419,8 +1026,8 @@ static int run_inv_tensor(exacto_ctx* c, const Operands& o, int cnt, bool p2only
     return 0;
 }
 
-static NttBatch contiguous(u64* data, long count_items, long poly_per_item, int prime_base, int period,
-                           int n) {
+NttBatch exacto::contiguous(u64* data, long count_items, long poly_per_item, int prime_base, int period,
+                            int n) {
     (void)count_items;
     NttBatch nb{};
     nb.src = data;
@@ -1828,7 +1435,7 @@ static int run_mul(exacto_ctx* c, const Operands& op, long P, u64* out, long out
 
 // ============================================================== C ABI: NTT / RNS
 
-static int check_ctx(exacto_ctx* c) {
+int exacto::check_ctx(exacto_ctx* c) {
     if (!c) return invalid_param("null context");
     HIP_TRY(hipSetDevice(c->device));
     return 0;
@@ -2089,8 +1696,8 @@ extern "C" int exacto_gadget_decompose_dev(exacto_ctx* c, const uint64_t* coeffs
 }
 
 // host-pointer wrappers: stage inputs in the context's io buffer, run the _dev entry, copy back
-static int host_call(exacto_ctx* c, const std::vector<std::pair<const void*, size_t>>& ins, size_t out_bytes,
-                     void* host_out, const std::function<int(std::vector<u64*>&, u64*)>& fn) {
+int exacto::host_call(exacto_ctx* c, const std::vector<std::pair<const void*, size_t>>& ins, size_t out_bytes,
+                      void* host_out, const std::function<int(std::vector<u64*>&, u64*)>& fn) {
     if (int e = check_ctx(c)) return e;
     size_t total = out_bytes;
     for (auto& in : ins) total += (in.second + 255) / 256 * 256;
@@ -2350,7 +1957,7 @@ static int mul_sum_plan(exacto_ctx* c, size_t B, size_t na, size_t nb, const uin
 }
 
 // DbfvParams::new checks (params/mod.rs:168-184)
-static int dbfv_params_check(size_t d, uint64_t base, uint64_t plain) {
+int exacto::dbfv_params_check(size_t d, uint64_t base, uint64_t plain) {
     if (base < 2) return invalid_param("base must be >= 2");
     if (d < 1) return invalid_param("num_digits must be >= 1");
     u128 bd = 1;
@@ -2940,241 +2547,6 @@ extern "C" int exacto_bfv_mul_sum_info(exacto_ctx* c, size_t* group_max, int* la
     return 0;
 }
 
-// ============================================================== decryption
-
-// bfv/encrypt.rs:111-178 for a batch: phase = sum_k c_k s^k (NTT domain), INTT, exact rounding.
-// ct = [B][polys][L][n] (stride ct_stride words per ciphertext), sk = [L][n] NTT domain.
-static int decrypt_batch(exacto_ctx* c, const u64* ct, size_t polys, long ct_stride, const u64* sk, u64* out,
-                         size_t B) {
-    if (polys < 1) return invalid_param("ciphertext has no polynomials");
-    if (B == 0) return 0;
-    const int L = c->L, n = c->n;
-    if (L >= 2 && (c->K < 1 || c->plain >= c->primes[L]))
-        return fail(EXACTO_ERR_NOT_IMPLEMENTED, "not yet implemented: GPU decryption needs plain_modulus below the "
-                                                "first internal auxiliary prime");
-    if (c->dec_buf.grow(B * L * poly_bytes(c))) return EXACTO_ERR_HIP;
-    launch_phase(ct, (int)polys, ct_stride, sk, c->dec_buf, (int)B, n, L, c->d_primes, c->stream);
-    CHECK_LAUNCH();
-    if (int e = run_ntt(c, contiguous(c->dec_buf, (long)B, L, 0, L, n), (long)B * L, true)) return e;
-    launch_decrypt_round(c->dec_buf, out, (int)B, n, L, c->d_crt, c->d_primes, c->plain, c->stream);
-    CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int exacto_bfv_decrypt_dev(exacto_ctx* c, const uint64_t* ct, size_t polys, const uint64_t* sk,
-                                      uint64_t* out, size_t B) {
-    if (int e = check_ctx(c)) return e;
-    return decrypt_batch(c, ct, polys, (long)polys * c->L * c->n, sk, out, B);
-}
-
-extern "C" int exacto_bfv_decrypt(exacto_ctx* c, const uint64_t* ct, size_t polys, const uint64_t* sk,
-                                  uint64_t* out, size_t B) {
-    if (!c) return invalid_param("null context");
-    return host_call(c, {{ct, B * polys * c->L * poly_bytes(c)}, {sk, c->L * poly_bytes(c)}}, B * poly_bytes(c), out,
-                     [&](std::vector<u64*>& dv, u64* o) { return exacto_bfv_decrypt_dev(c, dv[0], polys, dv[1], o, B); });
-}
-
-// dbfv/decrypt.rs:20-79: every limb decrypted with the BFV plaintext modulus t, then signed
-// recomposition mod p coefficient-wise (poly) or of coefficient 0 (scalar).
-static int dbfv_decrypt_common(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* ct,
-                               const uint64_t* sk, uint64_t* out, size_t B, bool scalar) {
-    if (int e = check_ctx(c)) return e;
-    if (int e = dbfv_params_check(d, base, plain)) return e;
-    if (!scalar && plain == 0)
-        return invalid_param("polynomial dBFV decrypt requires finite plain_modulus (plain_modulus=0 is scalar-only)");
-    if (B == 0) return 0;
-    const size_t nd = B * d;
-    if (c->dig_buf.grow(nd * poly_bytes(c))) return EXACTO_ERR_HIP;
-    if (int e = decrypt_batch(c, ct, 2, 2L * c->L * c->n, sk, c->dig_buf, nd)) return e;
-    launch_dbfv_recompose(c->dig_buf, out, (int)B, c->n, (int)d, base, plain, c->plain, scalar, c->stream);
-    CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int exacto_dbfv_decrypt_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* ct,
-                                       const uint64_t* sk, uint64_t* out, size_t B) {
-    return dbfv_decrypt_common(c, d, base, plain, ct, sk, out, B, true);
-}
-
-extern "C" int exacto_dbfv_decrypt_poly_dev(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
-                                            const uint64_t* ct, const uint64_t* sk, uint64_t* out, size_t B) {
-    return dbfv_decrypt_common(c, d, base, plain, ct, sk, out, B, false);
-}
-
-extern "C" int exacto_dbfv_decrypt(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain, const uint64_t* ct,
-                                   const uint64_t* sk, uint64_t* out, size_t B) {
-    if (!c) return invalid_param("null context");
-    return host_call(c, {{ct, B * d * 2 * c->L * poly_bytes(c)}, {sk, c->L * poly_bytes(c)}}, B * sizeof(u64), out,
-                     [&](std::vector<u64*>& dv, u64* o) {
-                         return exacto_dbfv_decrypt_dev(c, d, base, plain, dv[0], dv[1], o, B);
-                     });
-}
-
-extern "C" int exacto_dbfv_decrypt_poly(exacto_ctx* c, size_t d, uint64_t base, uint64_t plain,
-                                        const uint64_t* ct, const uint64_t* sk, uint64_t* out, size_t B) {
-    if (!c) return invalid_param("null context");
-    return host_call(c, {{ct, B * d * 2 * c->L * poly_bytes(c)}, {sk, c->L * poly_bytes(c)}}, B * poly_bytes(c), out,
-                     [&](std::vector<u64*>& dv, u64* o) {
-                         return exacto_dbfv_decrypt_poly_dev(c, d, base, plain, dv[0], dv[1], o, B);
-                     });
-}
-
-// ============================================================== modulus switch (bfv/modswitch.rs)
-
-// Argument checks shared by both forms, before anything is launched or copied.
-static int mod_switch_check(const exacto_ctx* c, size_t polys, size_t lin, size_t lout, int mode) {
-    if (lin <= 1) return invalid_param("cannot drop prime: only one modulus remaining");
-    if (lin > (size_t)c->L)
-        return invalid_param("mod_switch: limbs_in = " + std::to_string(lin) + " exceeds the context's " +
-                             std::to_string(c->L) + " ciphertext primes");
-    if (lout == 0) return invalid_param("mod_switch: limbs_out = 0 (at least one prime must remain)");
-    if (lout >= lin)
-        return invalid_param("mod_switch: limbs_out = " + std::to_string(lout) + " must be below limbs_in = " +
-                             std::to_string(lin));
-    if (polys == 0) return invalid_param("mod_switch: ciphertext has no polynomials");
-    if (mode != EXACTO_MODSWITCH_ROUND && mode != EXACTO_MODSWITCH_REFERENCE)
-        return invalid_param("mod_switch: unknown mode " + std::to_string(mode));
-    return 0;
-}
-
-// One drop l -> l - 1 of `rows` polynomials; the kernel path is chosen from the primes involved
-// (0 .. l-1), as run_ntt chooses the transforms'.
-static int run_drop_prime(exacto_ctx* c, const u64* in, u64* out, size_t rows, int l, bool round) {
-    const int L = c->L;
-    if (c->msw_w.empty()) {
-        c->msw_w.assign((size_t)L * L, 0);
-        c->msw_ws.assign((size_t)L * L, 0);
-        for (int j = 1; j < L; ++j)
-            for (int i = 0; i < j; ++i) {
-                const u64 qi = c->ctq[i], w = invmod_h(c->ctq[j] % qi, qi);
-                c->msw_w[(size_t)j * L + i] = w;
-                c->msw_ws[(size_t)j * L + i] = shoup_h(w, qi);
-            }
-    }
-    DropPrimeK K{};
-    for (int i = 0; i < l - 1; ++i) {
-        K.w[i] = c->msw_w[(size_t)(l - 1) * L + i];
-        K.ws[i] = c->msw_ws[(size_t)(l - 1) * L + i];
-    }
-    bool lazy = true, near60 = c->ntt_asm && c->ntt_asm_inv;
-    for (int t = 0; t < l; ++t) {
-        lazy &= c->primes[t] < (1ull << 60);
-        near60 &= c->primes[t] < (1ull << 60) && c->primes[t] > (1ull << 60) - (1ull << 32);
-    }
-    // algorithmic bytes: l rows read, l - 1 written
-    ProfScope ps(c, PK_MODSWITCH, (u64)rows, 8.0 * c->n * (double)rows * (2 * l - 1));
-    launch_drop_prime(in, out, (long)rows, l, round, K, c->logn, lazy, near60, c->d_primes, c->stream);
-    CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int exacto_bfv_mod_switch_dev(exacto_ctx* c, const uint64_t* ct, size_t polys, size_t lin, size_t lout,
-                                         int mode, uint64_t* out, size_t B) {
-    if (int e = check_ctx(c)) return e;
-    if (int e = mod_switch_check(c, polys, lin, lout, mode)) return e;
-    if (B == 0) return 0;
-    if (!ct || !out) return invalid_param("mod_switch: null ciphertext buffer");
-    if (((uintptr_t)ct | (uintptr_t)out) & 15) return invalid_param("mod_switch: ct and out must be 16-byte aligned");
-    const size_t n = (size_t)c->n, iw = polys * lin * n, ow = polys * lout * n;
-    if (out < ct + B * iw && ct < out + B * ow) return invalid_param("mod_switch: out overlaps ct");
-    const bool round = mode == EXACTO_MODSWITCH_ROUND;
-    if (lin - lout == 1) return run_drop_prime(c, ct, out, B * polys, (int)lin, round);
-    // several drops: chunk by chunk through two halves of the workspace, the last drop into out
-    const size_t C = std::min(c->chunk, B), half = C * polys * (lin - 1) * n;
-    if (c->msw_buf.grow(2 * half * sizeof(u64))) return EXACTO_ERR_HIP;
-    for (size_t i0 = 0; i0 < B; i0 += C) {
-        const size_t cnt = std::min(C, B - i0);
-        const u64* src = ct + i0 * iw;
-        int h = 0;
-        for (size_t l = lin; l > lout; --l) {
-            u64* dst = l - 1 == lout ? out + i0 * ow : c->msw_buf + h * half;
-            if (int e = run_drop_prime(c, src, dst, cnt * polys, (int)l, round)) return e;
-            src = dst;
-            h ^= 1;
-        }
-    }
-    return 0;
-}
-
-extern "C" int exacto_bfv_mod_switch(exacto_ctx* c, const uint64_t* ct, size_t polys, size_t lin, size_t lout, int mode,
-                                     uint64_t* out, size_t B) {
-    if (!c) return invalid_param("null context");
-    if (int e = mod_switch_check(c, polys, lin, lout, mode)) return e;
-    if (B == 0) return 0;
-    if (!ct || !out) return invalid_param("mod_switch: null ciphertext buffer");
-    const size_t iw = polys * lin * (size_t)c->n, ow = polys * lout * (size_t)c->n;
-    if (out < ct + B * iw && ct < out + B * ow) return invalid_param("mod_switch: out overlaps ct");
-    return host_call(c, {{ct, B * iw * sizeof(u64)}}, B * ow * sizeof(u64), out, [&](std::vector<u64*>& in, u64* o) {
-        return exacto_bfv_mod_switch_dev(c, in[0], polys, lin, lout, mode, o, B);
-    });
-}
-
-// ============================================================== noise (paper_repro.rs:238-281)
-
-// The decryption's phase and inverse NTT into dec_buf, then noise.hip: the maximum of the centred
-// residual |x - m Delta| over each group of `group` consecutive ciphertexts, L binary words each.
-// The per-workgroup partial maxima live behind the phase in dec_buf.  Delta's residues are uploaded
-// on the context's first use of them (as for encryption); nothing else waits for the device.
-static int delta_residues(exacto_ctx* c);
-static int noise_batch(exacto_ctx* c, const u64* ct, size_t polys, long ct_stride, const u64* sk, const u64* expected,
-                       u64* plain_out, u64* noise_out, size_t items, size_t group) {
-    if (polys < 1) return invalid_param("ciphertext has no polynomials");
-    if (items == 0) return 0;
-    const int L = c->L, n = c->n;
-    const bool round = !expected || plain_out;
-    if (round && L >= 2 && (c->K < 1 || c->plain >= c->primes[L]))
-        return fail(EXACTO_ERR_NOT_IMPLEMENTED, "not yet implemented: GPU decryption needs plain_modulus below the "
-                                                "first internal auxiliary prime");
-    if (int e = delta_residues(c)) return e;
-    const size_t phase_words = items * L * (size_t)n;
-    if (c->dec_buf.grow((phase_words + items * noise_chunks(n) * L) * sizeof(u64))) return EXACTO_ERR_HIP;
-    launch_phase(ct, (int)polys, ct_stride, sk, c->dec_buf, (int)items, n, L, c->d_primes, c->stream);
-    CHECK_LAUNCH();
-    if (int e = run_ntt(c, contiguous(c->dec_buf, (long)items, L, 0, L, n), (long)items * L, true)) return e;
-    launch_noise(c->dec_buf, expected, plain_out, c->dec_buf + phase_words, noise_out, (long)items, (int)group, n, L,
-                 c->d_crt, c->d_primes, c->d_delta, c->plain, round, c->stream);
-    CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int exacto_bfv_noise_dev(exacto_ctx* c, const uint64_t* ct, size_t polys, const uint64_t* sk,
-                                    const uint64_t* expected, uint64_t* plain_out, uint64_t* noise_out, size_t B) {
-    if (int e = check_ctx(c)) return e;
-    return noise_batch(c, ct, polys, (long)polys * c->L * c->n, sk, expected, plain_out, noise_out, B, 1);
-}
-
-extern "C" int exacto_bfv_noise(exacto_ctx* c, const uint64_t* ct, size_t polys, const uint64_t* sk,
-                                const uint64_t* expected, uint64_t* plain_out, uint64_t* noise_out, size_t B) {
-    if (!c) return invalid_param("null context");
-    // one staged output: [the plaintexts, if asked for][the noise words]
-    const size_t pw = plain_out ? B * (size_t)c->n : 0, nw = B * (size_t)c->L;
-    std::vector<u64> host(pw + nw);
-    std::vector<std::pair<const void*, size_t>> ins = {{ct, B * polys * c->L * poly_bytes(c)}, {sk, c->L * poly_bytes(c)}};
-    if (expected) ins.push_back({expected, B * poly_bytes(c)});
-    if (int e = host_call(c, ins, host.size() * sizeof(u64), host.data(), [&](std::vector<u64*>& dv, u64* o) {
-            return exacto_bfv_noise_dev(c, dv[0], polys, dv[1], expected ? dv[2] : nullptr, plain_out ? o : nullptr,
-                                        o + pw, B);
-        }))
-        return e;
-    if (pw) std::memcpy(plain_out, host.data(), pw * sizeof(u64));
-    if (nw) std::memcpy(noise_out, host.data() + pw, nw * sizeof(u64));
-    return 0;
-}
-
-extern "C" int exacto_dbfv_noise_dev(exacto_ctx* c, size_t d, const uint64_t* ct, const uint64_t* sk,
-                                     uint64_t* noise_out, size_t B) {
-    if (int e = check_ctx(c)) return e;
-    if (d < 1) return invalid_param("num_digits must be >= 1");
-    return noise_batch(c, ct, 2, 2L * c->L * c->n, sk, nullptr, nullptr, noise_out, B * d, d);
-}
-
-extern "C" int exacto_dbfv_noise(exacto_ctx* c, size_t d, const uint64_t* ct, const uint64_t* sk, uint64_t* noise_out,
-                                 size_t B) {
-    if (!c) return invalid_param("null context");
-    return host_call(c, {{ct, B * d * 2 * c->L * poly_bytes(c)}, {sk, c->L * poly_bytes(c)}}, B * c->L * sizeof(u64),
-                     noise_out, [&](std::vector<u64*>& dv, u64* o) { return exacto_dbfv_noise_dev(c, d, dv[0], dv[1], o, B); });
-}
-
 // dBFV multiplication chain with the guard-bypass semantics of paper_repro.rs:203-236 (and the
 // chain of bfv_host.rs:258-288 without its bootstrap): acc <- dbfv_mul(acc, y) `depth` times,
 // both mul_depth reset to 0 before every step; intermediates ping-pong between two
@@ -3413,7 +2785,7 @@ extern "C" int exacto_gen_relin_key_dev(exacto_ctx* c, const uint64_t* sk, doubl
 }
 
 // Delta_i = floor(Q / p) mod q_i (encrypt.rs:205-229), device copy in c->d_delta (with Shoup companions).
-static int delta_residues(exacto_ctx* c) {
+int exacto::delta_residues(exacto_ctx* c) {
     if (c->delta_ok) return 0;
     // Q as little-endian 64-bit words, then floor(Q / p) by long division, then mod each q_i
     std::vector<u64> Qw(1, 1);
@@ -5801,314 +5173,6 @@ extern "C" size_t exacto_prof_kernels(exacto_ctx* c, int kind, char* buf, size_t
         buf[k] = 0;
     }
     return out.size();
-}
-
-// ============================================================== RCCL collectives
-//
-// Keys are made once and broadcast over xGMI to every GPU (the reference builds them on one host,
-// keygen.rs:123-209); the limbs of a split dbfv_mul are gathered (never summed: an RCCL sum of
-// residues would overflow mod q).  librccl is opened at first use (dlopen of librccl.so.1, or
-// EXACTO_RCCL_LIB), so a process that already loaded RCCL (torch) shares that instance and the
-// library has no link-time dependency on it.  Communicators are plain ncclComm_t handles, passed as
-// void*: made here (exacto_rccl_comm_init) or by the caller's own RCCL.
-
-#include <rccl/rccl.h>
-
-namespace {
-struct Rccl {
-    bool ok = false;
-    std::string why;
-    ncclResult_t (*get_unique_id)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*comm_init_rank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*comm_destroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*comm_count)(const ncclComm_t, int*) = nullptr;
-    ncclResult_t (*comm_user_rank)(const ncclComm_t, int*) = nullptr;
-    ncclResult_t (*broadcast)(const void*, void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*all_gather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    const char* (*error_string)(ncclResult_t) = nullptr;
-    // optional (deadline handling): a communicator whose collective missed its deadline is aborted
-    ncclResult_t (*comm_abort)(ncclComm_t) = nullptr;
-    ncclResult_t (*async_error)(ncclComm_t, ncclResult_t*) = nullptr;
-};
-
-const Rccl& rccl() {
-    static const Rccl r = [] {
-        Rccl x;
-        const char* env = getenv("EXACTO_RCCL_LIB");
-        void* h = dlopen(env ? env : "librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-        if (!h) { x.why = std::string("cannot open RCCL: ") + dlerror(); return x; }
-        bool all = true;
-        auto sym = [&](auto& f, const char* name) {
-            f = reinterpret_cast<std::remove_reference_t<decltype(f)>>(dlsym(h, name));
-            all &= f != nullptr;
-        };
-        sym(x.get_unique_id, "ncclGetUniqueId");
-        sym(x.comm_init_rank, "ncclCommInitRank");
-        sym(x.comm_destroy, "ncclCommDestroy");
-        sym(x.comm_count, "ncclCommCount");
-        sym(x.comm_user_rank, "ncclCommUserRank");
-        sym(x.broadcast, "ncclBroadcast");
-        sym(x.all_gather, "ncclAllGather");
-        sym(x.error_string, "ncclGetErrorString");
-        x.ok = all;
-        x.comm_abort = reinterpret_cast<decltype(x.comm_abort)>(dlsym(h, "ncclCommAbort"));
-        x.async_error = reinterpret_cast<decltype(x.async_error)>(dlsym(h, "ncclCommGetAsyncError"));
-        if (!all) x.why = "RCCL library lacks a required symbol";
-        return x;
-    }();
-    return r;
-}
-}  // namespace
-
-#define RCCL_TRY(x)                                                                                      \
-    do {                                                                                                 \
-        const ncclResult_t r_ = (x);                                                                     \
-        if (r_ != ncclSuccess)                                                                           \
-            return fail(EXACTO_ERR_HIP, std::string("RCCL error: ") + rccl().error_string(r_) + " (" #x ")"); \
-    } while (0)
-
-static int rccl_ready() {
-    if (!rccl().ok) return fail(EXACTO_ERR_HIP, "RCCL error: " + rccl().why);
-    return 0;
-}
-
-extern "C" int exacto_rccl_unique_id(uint8_t* id) {
-    if (!id) return invalid_param("null id buffer");
-    if (int e = rccl_ready()) return e;
-    ncclUniqueId u;
-    RCCL_TRY(rccl().get_unique_id(&u));
-    std::memcpy(id, u.internal, NCCL_UNIQUE_ID_BYTES);
-    return 0;
-}
-
-// Deadline of the blocking RCCL steps (communicator init, the agreement all-gather, exacto_rccl_sync):
-// $EXACTO_RCCL_TIMEOUT_S seconds (default 300; 0 = wait forever).  A rank that never joins makes the
-// others fail with EXACTO_ERR_HIP "RCCL error: ... timed out" instead of blocking their process for
-// good (the driver's 8-GPU run has one time limit for everything).
-static double rccl_timeout_s() {
-    const char* e = getenv("EXACTO_RCCL_TIMEOUT_S");
-    return e ? atof(e) : 300.0;
-}
-
-// Communicators aborted after a missed deadline: RCCL has freed them, so destroy must not touch them.
-static std::mutex g_aborted_mu;
-static std::set<void*> g_aborted;
-
-static int rccl_abort_timeout(void* comm, const std::string& what, double secs) {
-    if (rccl().comm_abort) {
-        (void)rccl().comm_abort((ncclComm_t)comm);
-        std::lock_guard<std::mutex> g(g_aborted_mu);
-        g_aborted.insert(comm);
-    }
-    return fail(EXACTO_ERR_HIP, "RCCL error: " + what + " timed out after " + std::to_string((int)secs) +
-                                    " s (a rank did not join); communicator aborted");
-}
-
-// Waits for the context stream (the collectives enqueued on it) with the deadline: polls hipStreamQuery
-// and the communicator's asynchronous error.  On expiry the communicator is aborted (RCCL then stops its
-// kernels) and the call fails; it never returns with a collective still blocking the stream silently.
-static int rccl_stream_wait(exacto_ctx* c, void* comm, const char* what) {
-    const double lim = rccl_timeout_s();
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned it = 0;; ++it) {
-        const hipError_t q = hipStreamQuery(c->stream);
-        if (q == hipSuccess) return 0;
-        if (q != hipErrorNotReady) return fail(EXACTO_ERR_HIP, std::string("HIP error: ") + hipGetErrorString(q) + " (" + what + ")");
-        if (rccl().async_error) {
-            ncclResult_t ae = ncclSuccess;
-            if (rccl().async_error((ncclComm_t)comm, &ae) == ncclSuccess && ae != ncclSuccess && ae != ncclInProgress)
-                return fail(EXACTO_ERR_HIP, std::string("RCCL error: ") + rccl().error_string(ae) + " (" + what + ")");
-        }
-        const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (lim > 0 && el > lim) return rccl_abort_timeout(comm, what, lim);
-        std::this_thread::sleep_for(std::chrono::microseconds(it < 100 ? 20 : 1000));
-    }
-}
-
-extern "C" int exacto_rccl_comm_init(void** comm, int nranks, const uint8_t* id, int rank, int device) {
-    if (!comm || !id) return invalid_param("null argument");
-    if (nranks < 1 || rank < 0 || rank >= nranks) return invalid_param("rank out of range");
-    if (int e = rccl_ready()) return e;
-    HIP_TRY(hipSetDevice(device));
-    ncclUniqueId u;
-    std::memcpy(u.internal, id, NCCL_UNIQUE_ID_BYTES);
-    // ncclCommInitRank blocks until every rank has joined: it runs on a helper thread so that the
-    // caller's wait has a deadline.  On expiry the helper is left behind (it holds only its own copy
-    // of the arguments) and the call fails; the caller is expected to end the process.
-    struct InitState {
-        std::mutex mu;
-        std::condition_variable cv;
-        bool done = false;
-        ncclResult_t r = ncclSuccess;
-        ncclComm_t cm = nullptr;
-    };
-    auto st = std::make_shared<InitState>();
-    std::thread([st, nranks, u, rank, device] {
-        (void)hipSetDevice(device);
-        ncclComm_t cm = nullptr;
-        const ncclResult_t r = rccl().comm_init_rank(&cm, nranks, u, rank);
-        std::lock_guard<std::mutex> g(st->mu);
-        st->r = r;
-        st->cm = cm;
-        st->done = true;
-        st->cv.notify_all();
-    }).detach();
-    const double lim = rccl_timeout_s();
-    std::unique_lock<std::mutex> lk(st->mu);
-    if (lim > 0) {
-        if (!st->cv.wait_for(lk, std::chrono::duration<double>(lim), [&] { return st->done; }))
-            return fail(EXACTO_ERR_HIP, "RCCL error: ncclCommInitRank timed out after " + std::to_string((int)lim) +
-                                            " s (a rank did not join)");
-    } else {
-        st->cv.wait(lk, [&] { return st->done; });
-    }
-    if (st->r != ncclSuccess)
-        return fail(EXACTO_ERR_HIP, std::string("RCCL error: ") + rccl().error_string(st->r) + " (ncclCommInitRank)");
-    *comm = st->cm;
-    return 0;
-}
-
-extern "C" int exacto_rccl_comm_destroy(void* comm) {
-    if (!comm) return 0;
-    if (int e = rccl_ready()) return e;
-    {
-        std::lock_guard<std::mutex> g(g_aborted_mu);
-        if (g_aborted.erase(comm)) return 0;   // freed by ncclCommAbort
-    }
-    RCCL_TRY(rccl().comm_destroy((ncclComm_t)comm));
-    return 0;
-}
-
-extern "C" int exacto_rccl_sync(exacto_ctx* c, void* comm) {
-    if (int e = check_ctx(c)) return e;
-    if (!comm) return invalid_param("null communicator");
-    if (int e = rccl_ready()) return e;
-    return rccl_stream_wait(c, comm, "collective on the context stream");
-}
-
-extern "C" int exacto_rccl_comm_count(void* comm, int* nranks) {
-    if (!comm || !nranks) return invalid_param("null argument");
-    if (int e = rccl_ready()) return e;
-    RCCL_TRY(rccl().comm_count((ncclComm_t)comm, nranks));
-    return 0;
-}
-
-// In-place broadcast of `words` u64 at buf from root's buffer, enqueued on the context stream.
-// Checks the communicator and the root first; *my_rank (optional) receives this rank.
-static int rccl_check(void* comm, int root, int* my_rank) {
-    if (!comm) return invalid_param("null communicator");
-    if (int e = rccl_ready()) return e;
-    int nr = 0;
-    RCCL_TRY(rccl().comm_count((ncclComm_t)comm, &nr));
-    if (root < 0 || root >= nr) return invalid_param("root out of range");
-    if (my_rank) RCCL_TRY(rccl().comm_user_rank((ncclComm_t)comm, my_rank));
-    return 0;
-}
-
-static int rccl_bcast(exacto_ctx* c, void* comm, int root, u64* buf, size_t words) {
-    if (int e = rccl_check(comm, root, nullptr)) return e;
-    if (!words) return 0;
-    RCCL_TRY(rccl().broadcast(buf, buf, words, ncclUint64, root, (ncclComm_t)comm, c->stream));
-    return 0;
-}
-
-// Agreement step of a collective call: every rank contributes {its num_keys, its own verdict} and
-// all-gathers everyone's, so that every rank takes the same decision (proceed or InvalidParam)
-// before any rank resizes its key or enqueues the key broadcast.  A mismatch therefore fails on all
-// ranks instead of leaving the others blocked in a broadcast the failing rank never joins.
-static int rccl_agree(exacto_ctx* c, void* comm, u64 mine, u64 ok, bool* agreed, std::string* why) {
-    *agreed = false;
-    int nr = 0;
-    RCCL_TRY(rccl().comm_count((ncclComm_t)comm, &nr));
-    DevBuf<u64> dev;
-    if (int e = dev.alloc(sizeof(u64) * 2 * (nr + 1))) return e;
-    std::vector<u64> host(2 * (size_t)(nr + 1));
-    host[0] = mine;
-    host[1] = ok;
-    int rc = 0;
-    if (hipMemcpyAsync(dev, host.data(), 2 * sizeof(u64), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        rc = fail(EXACTO_ERR_HIP, "HIP error: hipMemcpyAsync (agreement header)");
-    else {
-        const ncclResult_t r = rccl().all_gather(dev, dev + 2, 2, ncclUint64, (ncclComm_t)comm, c->stream);
-        if (r != ncclSuccess)
-            rc = fail(EXACTO_ERR_HIP, std::string("RCCL error: ") + rccl().error_string(r) + " (ncclAllGather)");
-        else if (hipMemcpyAsync(host.data() + 2, dev + 2, 2 * sizeof(u64) * nr, hipMemcpyDeviceToHost, c->stream) !=
-                     hipSuccess ||
-                 (rc = rccl_stream_wait(c, comm, "agreement all-gather")) != 0) {
-            if (!rc) rc = fail(EXACTO_ERR_HIP, "HIP error: agreement header read-back");
-        }
-    }
-    if (rc) {   // a timed-out all-gather may still own `dev`, and a release would wait for it: leave the
-                // block to a holder that is never destroyed (the process is ending)
-        (void)new DevBuf<u64>(std::move(dev));
-        return rc;
-    }
-    (void)hipStreamSynchronize(c->stream);
-    for (int r = 0; r < nr; ++r) {
-        if (!host[2 + 2 * r + 1]) {
-            *why = "rank " + std::to_string(r) + " rejected the call";
-            return 0;
-        }
-        if (host[2 + 2 * r] != host[2]) {
-            *why = "ranks disagree on num_keys (rank 0: " + std::to_string(host[2]) + ", rank " + std::to_string(r) +
-                   ": " + std::to_string(host[2 + 2 * r]) + ")";
-            return 0;
-        }
-    }
-    *agreed = true;
-    return 0;
-}
-
-// Every check runs before the resident key is touched: a failed call (bad root, no RCCL, a root
-// without a loaded key of that size, ranks passing different num_keys) leaves every rank's key
-// exactly as it was and returns InvalidParam on every rank (rccl_agree).  The root broadcasts its
-// resident key as loaded (never resized); a receiving rank's buffer is (re)sized and marked loaded
-// only once the broadcast into it has been enqueued.
-extern "C" int exacto_ctx_broadcast_relin_key(exacto_ctx* c, void* comm, int root, size_t num_keys) {
-    if (int e = check_ctx(c)) return e;
-    int me = -1;
-    if (int e = rccl_check(comm, root, &me)) return e;
-    const size_t words = num_keys * 2 * c->L * (size_t)c->n;
-    const bool root_ok = c->rlk_loaded && c->rlk_keys == num_keys;
-    std::string why;
-    bool agreed = false;
-    if (int e = rccl_agree(c, comm, num_keys, me == root ? root_ok : 1, &agreed, &why)) return e;
-    if (!agreed) {
-        if (me == root && !root_ok)
-            why = "broadcast root has no resident relinearization key of " + std::to_string(num_keys) + " rows";
-        return invalid_param(why);
-    }
-    if (me == root) {
-        if (!words) return 0;
-        RCCL_TRY(rccl().broadcast(c->d_rlk, c->d_rlk, words, ncclUint64, root, (ncclComm_t)comm, c->stream));
-        return 0;
-    }
-    u64* dst = exacto_ctx_relin_key_buffer(c, num_keys);
-    if (!dst) return fail(EXACTO_ERR_HIP, "HIP error: relinearization key allocation failed");
-    if (words) {
-        const ncclResult_t r = rccl().broadcast(dst, dst, words, ncclUint64, root, (ncclComm_t)comm, c->stream);
-        if (r != ncclSuccess) {
-            c->rlk_loaded = false;   // the buffer's contents are undefined now
-            return fail(EXACTO_ERR_HIP, std::string("RCCL error: ") + rccl().error_string(r) + " (ncclBroadcast)");
-        }
-    }
-    return 0;
-}
-
-extern "C" int exacto_broadcast_galois_key(exacto_ctx* c, void* comm, int root, uint64_t* gk, size_t num_keys) {
-    if (int e = check_ctx(c)) return e;
-    if (num_keys && !gk) return invalid_param("null Galois key");
-    return rccl_bcast(c, comm, root, gk, num_keys * 2 * c->L * (size_t)c->n);
-}
-
-extern "C" int exacto_rccl_allgather_u64(exacto_ctx* c, void* comm, const uint64_t* send, uint64_t* recv, size_t count) {
-    if (int e = check_ctx(c)) return e;
-    if (!comm) return invalid_param("null communicator");
-    if (count && (!send || !recv)) return invalid_param("null buffer");
-    if (int e = rccl_ready()) return e;
-    if (!count) return 0;
-    RCCL_TRY(rccl().all_gather(send, recv, count, ncclUint64, (ncclComm_t)comm, c->stream));
-    return 0;
 }
 
 extern "C" const char* exacto_version(void) { return "exacto-hip 0.4.0 (gfx950)"; }

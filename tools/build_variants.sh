@@ -6,11 +6,15 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 make -C $R/exacto_amd/csrc -s
 OUT=$R/build/variants; mkdir -p $OUT
 H="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC"
+# every object of the library's own build (the Makefile's SRCS) except ntt.o, plus the variant's ntt_<name>.o
+OBJS=$(for s in $(sed -n 's/^SRCS := //p' $R/exacto_amd/csrc/Makefile); do [ $s = ntt.hip ] || echo $R/build/obj/${s%.hip}.o; done)
+link() {  # name
+  $H --offload-arch=gfx950 -shared -fPIC -o $OUT/$1.so $OBJS $OUT/ntt_$1.o -ldl
+}
 build() {  # name, flags...
   local name=$1; shift
   $H "$@" -c $R/exacto_amd/csrc/ntt.hip -o $OUT/ntt_$name.o
-  $H --offload-arch=gfx950 -shared -fPIC -o $OUT/$name.so $R/build/obj/context.o $R/build/obj/kernels.o \
-    $R/build/obj/keygen.o $R/build/obj/plain.o $R/build/obj/ks32.o $OUT/ntt_$name.o -ldl
+  link $name
 }
 # a variant whose generated rounds differ (gen_ntt_asm.py env switches): ntt.hip is compiled from a
 # copy next to the regenerated ntt_asm.inc (quoted includes search the file's own directory first)
@@ -20,8 +24,7 @@ build_gen() {  # name, env assignment
   cp $R/exacto_amd/csrc/ntt.hip $D/
   env "$@" python3 -c "import sys; sys.path.insert(0, '$R/tools'); import gen_ntt_asm as G; G.OUT = '$D/ntt_asm.inc'; G.main()" > /dev/null
   $H -I $R/exacto_amd/csrc -c $D/ntt.hip -o $OUT/ntt_$name.o
-  $H --offload-arch=gfx950 -shared -fPIC -o $OUT/$name.so $R/build/obj/context.o $R/build/obj/kernels.o \
-    $R/build/obj/keygen.o $R/build/obj/plain.o $R/build/obj/ks32.o $OUT/ntt_$name.o -ldl
+  link $name
 }
 for v in "$@"; do
   case $v in

@@ -32,7 +32,7 @@ SHAPES = {
     "cfg3": dict(n=4096, q=Q4[:3], t=65537, polys=2, B=1024),
     "cfg5": dict(n=8192, q=Q4, t=1040407, polys=2, B=256),
 }
-PK_MODSWITCH = 18   # context.hip ProfKind
+PK_MODSWITCH = 18   # runtime.hpp ProfKind
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--shape", choices=list(SHAPES) + ["all"], default="all")

@@ -35,7 +35,7 @@ SHAPES = {
     "cfg3_k32": dict(n=4096, q=Q4[:3], t=65537, gbase=0, B=32, K=32),
     "cfg5_k8": dict(n=8192, q=Q4, t=1040407, gbase=256, B=8, K=8),
 }
-# profiled kernel families (context.hip ProfKind)
+# profiled kernel families (runtime.hpp ProfKind)
 KINDS = {0: "fwd_ntt", 1: "inv_ntt", 2: "tensor", 4: "lift", 5: "scale", 6: "ks_digits", 7: "ks_mac", 8: "ks_crt",
          9: "pairsum", 10: "psum_scale", 12: "digit_sum", 13: "combine", 17: "group_sum"}
 
