@@ -212,6 +212,15 @@ _SIGS = [
     ("exacto_bfv_rotate_hoisted_dev", [_P, _P, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_linear_transform", [_P, _P, _P, _P, _P, _SZ], C.c_int),
     ("exacto_bfv_linear_transform_dev", [_P, _P, _P, _P, _P, _SZ], C.c_int),
+    ("exacto_dbfv_rotate_hoisted", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
+    ("exacto_dbfv_rotate_hoisted_dev", [_P, _P, _SZ, _P, _P, _SZ], C.c_int),
+    ("exacto_dbfv_diagonals_create", [_P, _SZ, _SZ, _P, C.POINTER(_P)], C.c_int),
+    ("exacto_dbfv_diagonals_create_dev", [_P, _SZ, _SZ, _P, C.POINTER(_P)], C.c_int),
+    ("exacto_dbfv_diagonals_destroy", [_P], None),
+    ("exacto_ctx_set_dbfv_lt_fused", [_P, C.c_int], C.c_int),
+    ("exacto_dbfv_diagonals_info", [_P, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(C.c_int)], C.c_int),
+    *[(f"exacto_dbfv_linear_transform{sfx}", [_P, _P, _SZ, _U64, _U64, _P, _P, _P, _SZ, _P, _P], C.c_int)
+      for sfx in ("", "_dev", "_prepared", "_prepared_dev")],
     ("exacto_last_error", [C.c_char_p, _SZ], _SZ),
     ("exacto_prof_enable", [_P, C.c_int], C.c_int),
     ("exacto_prof_read", [_P, C.c_int, C.POINTER(_U64), C.POINTER(C.c_double),
@@ -388,6 +397,46 @@ class GaloisKeySet:
     def close(self):
         if self._h:
             self.ctx._lib.exacto_galois_keyset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DbfvDiagonals:
+    """Wide public diagonals lifted once for dBFV linear transforms (exacto_dbfv_diagonals_create): pts
+    [R][d][n] plaintext coefficients -> a device buffer [R][d][L][n].  Holds a reference to its HipContext, so
+    the context outlives it; close() (or garbage collection) releases the device memory.  `fused`: the route
+    a transform of d digits took on that context when the handle was made (False: the staged route, the default;
+    True: the fused kernel, after set_dbfv_lt_fused(True))."""
+
+    def __init__(self, ctx: "HipContext", d: int, pts, R: int | None = None, dev: bool = False):
+        self.ctx = ctx
+        if dev:
+            pp, r = ctx._p(pts), int(R or 0)
+        else:
+            p = _u64(pts)
+            if p.ndim != 3 or p.shape[1:] != (d, ctx.n):
+                raise ValueError(f"pts must be a [R][{d}][{ctx.n}] array")
+            pp, r = (p.ctypes.data if p.size else None), p.shape[0]
+        h = C.c_void_p()
+        fn = ctx._lib.exacto_dbfv_diagonals_create_dev if dev else ctx._lib.exacto_dbfv_diagonals_create
+        check(fn(ctx._h, d, r, pp, C.byref(h)))
+        self._h = h
+        rr, dd, f = C.c_size_t(), C.c_size_t(), C.c_int()
+        check(ctx._lib.exacto_dbfv_diagonals_info(h, C.byref(rr), C.byref(dd), C.byref(f)))
+        self.R, self.d, self.fused = int(rr.value), int(dd.value), bool(f.value)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            self.ctx._lib.exacto_dbfv_diagonals_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -1197,6 +1246,78 @@ class HipContext:
     def dbfv_swap_rows(self, ct, gk) -> np.ndarray:
         """The two rows of the wide slots exchanged: dbfv_apply_automorphism with 2n - 1 and its key."""
         return self.dbfv_apply_automorphism(ct, galois_element_swap_rows(self.n), gk)
+
+    # ---- dBFV hoisted rotations and slot linear transforms with wide diagonals (exacto_dbfv_linear_transform*)
+    def dbfv_rotate_hoisted(self, ct, keyset: "GaloisKeySet") -> np.ndarray:
+        """ct [B][d][2][L][n] -> [B][R][d][2][L][n]: limb j of out[b][r] is bfv_rotate_hoisted's [b*d + j][r]."""
+        ct = _u64(ct)
+        if ct.ndim != 5:
+            raise ValueError("ct must be [B][d][2][L][n]")
+        B, d = ct.shape[:2]
+        out = np.zeros((B, keyset.R, d, 2, self.L, self.n), dtype=np.uint64)
+        check(self._lib.exacto_dbfv_rotate_hoisted(self._h, keyset.handle, d, ct.ctypes.data if ct.size else None,
+                                                   out.ctypes.data if out.size else None, B))
+        return out
+
+    def dbfv_rotate_hoisted_dev(self, d, ct, keyset: "GaloisKeySet", out, batch):
+        check(self._lib.exacto_dbfv_rotate_hoisted_dev(self._h, keyset.handle, d, self._p(ct), self._p(out), batch))
+
+    def dbfv_rotate_rows_many(self, ct, steps, keyset: "GaloisKeySet") -> np.ndarray:
+        """Both rows of the wide slots left by every steps[r] at once: ct [B][d][2][L][n] -> [B][R][d][2][L][n];
+        keyset holds the elements 3^steps[r] mod 2n in this order (rotate_rows_keyset)."""
+        want = [galois_element_rotate_rows(self.n, int(s)) for s in steps]
+        if [e % (2 * self.n) for e in keyset.elements] != want:
+            raise ValueError("keyset does not hold the elements of these steps in this order")
+        return self.dbfv_rotate_hoisted(ct, keyset)
+
+    def set_dbfv_lt_fused(self, on: bool):
+        """True: dBFV linear transforms on the limb-wise key switch with d <= 8 take the fused kernel instead of
+        the staged route, the default (tests and measurements); no result depends on it."""
+        check(self._lib.exacto_ctx_set_dbfv_lt_fused(self._h, 1 if on else 0))
+
+    def dbfv_diagonals(self, d, pts) -> "DbfvDiagonals":
+        """pts [R][d][n] plaintext coefficients (host) -> diagonals lifted once for dbfv_linear_transform."""
+        return DbfvDiagonals(self, d, pts)
+
+    def dbfv_diagonals_dev(self, d, pts, R) -> "DbfvDiagonals":
+        """The same from device memory pts [R][d][n] (may be released afterwards)."""
+        return DbfvDiagonals(self, d, pts, R, dev=True)
+
+    def dbfv_linear_transform(self, d, base, plain, ct, keyset: "GaloisKeySet", pts, depth_ct=None):
+        """ct [B][d][2][L][n]; pts [R][d][n] plaintext coefficients or a DbfvDiagonals -> (out [B][d][2][L][n],
+        mul_depth [B]): reduce(sum_r pts[r] * rotation r), dbfv_plain_mul_sum over the hoisted rotations."""
+        ct = _u64(ct)
+        if ct.ndim != 5 or ct.shape[1] != d:
+            raise ValueError(f"ct must be [B][{d}][2][L][n]")
+        B = ct.shape[0]
+        out = np.zeros_like(ct)
+        dc = self._depths(depth_ct, B)
+        dout = np.zeros(B, dtype=np.uint32)
+        if isinstance(pts, DbfvDiagonals):
+            fn, pp = self._lib.exacto_dbfv_linear_transform_prepared, pts.handle
+        else:
+            pts = _u64(pts)
+            if pts.shape != (keyset.R, d, self.n):
+                raise ValueError(f"pts must be a [{keyset.R}][{d}][{self.n}] array")
+            fn, pp = self._lib.exacto_dbfv_linear_transform, pts.ctypes.data
+        check(fn(self._h, keyset.handle, d, base, plain, ct.ctypes.data, pp, out.ctypes.data, B, _ptr(dc),
+                 dout.ctypes.data))
+        return out, dout
+
+    def dbfv_linear_transform_dev(self, d, base, plain, ct, keyset: "GaloisKeySet", pts, out, batch, depth_ct=None):
+        """pts: a device buffer [R][d][n] or a DbfvDiagonals."""
+        dc = self._depths(depth_ct, batch)
+        if isinstance(pts, DbfvDiagonals):
+            fn, pp = self._lib.exacto_dbfv_linear_transform_prepared_dev, pts.handle
+        else:
+            fn, pp = self._lib.exacto_dbfv_linear_transform_dev, self._p(pts)
+        check(fn(self._h, keyset.handle, d, base, plain, self._p(ct), pp, self._p(out), batch, _ptr(dc), None))
+
+    def dbfv_batch_linear_transform(self, d, base, plain, ct, keyset: "GaloisKeySet", wide_diagonals, depth_ct=None):
+        """Slot-wise sum_r W_r[s] * x[rot_r(s)] mod p: wide_diagonals [R][n] slot-encoded on the device
+        (dbfv_batch_encode), then dbfv_linear_transform.  Returns (out, mul_depth [B])."""
+        pts = self.dbfv_batch_encode(d, base, plain, wide_diagonals)
+        return self.dbfv_linear_transform(d, base, plain, ct, keyset, pts, depth_ct)
 
     def gen_trace_galois_keys(self, sk, key, stream=0, elements=None, sigma=3.2):
         """gen_trace_galois_keys / gen_all_galois_keys (coeffs_to_slots.rs:151-197): one key per element,

@@ -4151,34 +4151,55 @@ static int hoist_check(exacto_ctx* c, const exacto_galois_keyset* ks) {
     return 0;
 }
 
+// What the dBFV entry points add to a hoisted pass: the B limbs are B / d whole dBFV ciphertexts
+struct HoistDbfv {
+    int d = 1;                  // group size: output (limb, r) goes to hoist_out_index(limb, r, R, d)
+    size_t r0 = 0, rc = 0;      // the key set's rotations [r0, r0 + rc) only (rc = 0: all of them)
+    // linear transform: the product's tables, its pl the lifted diagonals [rc][d][L][n] of those rotations;
+    // out [B / d][d][2][L][n] = (accum ? out : 0) + reduce(sum_r pl_r * rotation r)
+    const DbfvPlainArgs* prod = nullptr;
+    bool fused = false;         // limb-wise key switch only: dbfv_hoist.hip instead of rotations + product
+};
+
 // out[b][r] = (sigma_r(c0) + sum_g sigma_r(d_g) k_{r,g,0}, sum_g sigma_r(d_g) k_{r,g,1}), d_g the digits of c1
 // itself; pts != nullptr: out[b] = sum_r pt_r out[b][r] instead (pts [R][n] plaintext coefficients).
 static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* ct, const u64* pts, bool lt, u64* out,
-                      size_t B) {
+                      size_t B, const HoistDbfv* dv = nullptr) {
     if (int e = check_ctx(c)) return e;
     if (int e = hoist_check(c, ks)) return e;
     if (B == 0) return 0;
     if (!ct || !out || (lt && !pts)) return invalid_param("null argument");
-    const int n = c->n, L = c->L, R = (int)ks->R, guse = ks->guse;
+    const int gs = dv ? dv->d : 1;
+    const size_t r0 = dv ? dv->r0 : 0, Rz = dv && dv->rc ? dv->rc : ks->R;
+    const bool prod = dv && dv->prod;
+    const int n = c->n, L = c->L, R = (int)Rz, guse = ks->guse;
     const long Ln = (long)L * n;
-    const size_t in_words = B * 2 * (size_t)Ln, out_words = in_words * (lt ? 1 : ks->R);
+    const size_t in_words = B * 2 * (size_t)Ln, out_words = in_words * (lt || prod ? 1 : Rz);
     if (out < ct + in_words && ct < out + out_words) return invalid_param("out must not overlap ct");
     const bool d16 = c->digit16 && c->gbase <= 65536;
     const bool k32 = ks->k32;
+    const bool fused = prod && dv->fused && !k32;
     const Ks32Basis& kb = c->kn;
     if (lt)
         if (int e = lift_plain(c, pts, R, false)) return e;   // pl_buf [R][L][n], made before the fork
-    // chunk: the 31-bit path's sums (S / 2 outputs per rotation) and, for the linear transform, its
-    // rotations stay within R outputs per chunk item of c->chunk; one launch's blocks within 2^30
+    // the rotations' slice of the set
+    const uint32_t* perm = ks->d_perm + r0 * (size_t)n;
+    const unsigned char* ident = ks->d_ident + r0;
+    const size_t key_off = r0 * (size_t)guse * 2 * (size_t)Ln;
+    // chunk: the 31-bit path's sums (S / 2 outputs per rotation) and, for the linear transforms, its
+    // rotations stay within R outputs per chunk item of c->chunk; one launch's blocks within 2^30; whole
+    // dBFV ciphertexts (max(1, chunk / d) of them)
     size_t C = std::min<size_t>(c->chunk, B);
-    if (k32) C = std::max<size_t>(1, C * 2 / (size_t)(kb.S + (lt ? 2 : 0)));
+    if (k32) C = std::max<size_t>(1, C * 2 / (size_t)(kb.S + (lt || prod ? 2 : 0)));
     const size_t nblk = (size_t)((Ln + 255) / 256);
-    C = std::max<size_t>(1, std::min<size_t>(C, ((size_t)1 << 30) / (nblk * ks->R)));
+    if (nblk * Rz * (size_t)gs > ((size_t)1 << 30)) return invalid_param("batch too large");
+    C = std::max<size_t>(1, std::min<size_t>(C, ((size_t)1 << 30) / (nblk * Rz)));
+    C = std::max<size_t>(1, C / (size_t)gs) * (size_t)gs;
     const long nchunks = (long)((B + C - 1) / C);
     const int nl_max = LanePass::count(c, nchunks);
     // per-lane scratch, declared before the LanePass: allocated before the fork, released after the join
-    const size_t u_words = k32 ? C * ks->R * 2 * L * (size_t)kb.S * n : 0;            // uint32
-    const size_t h_words = (k32 && lt) ? C * ks->R * 2 * (size_t)Ln : 0;              // u64
+    const size_t u_words = k32 ? C * Rz * 2 * L * (size_t)kb.S * n : 0;               // uint32
+    const size_t h_words = ((k32 && lt) || (prod && !fused)) ? C * Rz * 2 * (size_t)Ln : 0;   // u64
     Scratch us, hs;
     if (u_words) HIP_TRY(us.alloc(u_words * nl_max * sizeof(uint32_t), c->stream, c->pool, c->debug_scratch));
     if (h_words) HIP_TRY(hs.alloc(h_words * nl_max * sizeof(u64), c->stream, c->pool, c->debug_scratch));
@@ -4189,7 +4210,16 @@ static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* 
         const int li = (int)((s0 / C) % (size_t)pass.lanes());
         LaneGuard lane = pass.chunk((long)(s0 / C));
         const u64* src = ct + s0 * 2 * Ln;
-        u64* dst = out + s0 * 2 * Ln * (lt ? 1 : ks->R);
+        u64* dst = out + s0 * 2 * Ln * (lt || prod ? 1 : Rz);
+        // the staged dBFV product: H [cnt / d][R][d][2][L][n] is the term-major operand of dbfv_plain.hip as it is
+        auto product = [&](const u64* H) {
+            DbfvPlainArgs a = *dv->prod;
+            a.cts = H;
+            a.ct_term_stride = (long)gs * 2 * Ln; a.ct_item_stride = (long)R * a.ct_term_stride;
+            a.K = R; a.polys = 2;
+            a.out = dst; a.items = cnt / gs;
+            launch_dbfv_plain_mul(a, c->stream);
+        };
         if (guse > 0) {
             // c1 alone back to coefficients, its exact CRT and gadget digits, one digit transform
             NttBatch nb{};
@@ -4203,7 +4233,7 @@ static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* 
         }
         if (k32) {
             uint32_t* U = us.as<uint32_t>() + (size_t)li * u_words;
-            u64* H = lt ? hs.as<u64>() + (size_t)li * h_words : dst;
+            u64* H = h_words ? hs.as<u64>() + (size_t)li * h_words : dst;
             {
                 ProfScope pd(c, PK_KS_DIGITS, (u64)cnt * guse * kb.S, (2.0 + 4.0 * kb.S) * n * (double)cnt * guse);
                 ks32_digits(c->ws.D16, c->ws.DS, cnt, guse, kb.S, c->logn, kb.d_p32, kb.mac_form, c->stream);
@@ -4213,8 +4243,8 @@ static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* 
             {
                 ProfScope pm(c, PK_KS_MAC, (u64)cnt * R * 2 * L * kb.S,
                              4.0 * n * kb.S * ((double)cnt * R * (guse + 2 * L) + (double)R * guse * 2 * L));
-                ks32_mac_hoist(c->ws.DS, ks->d_rs, U, ks->d_perm, ks->d_ident, cnt, R, guse, L, kb.S, n, kb.d_p32,
-                               kb.mac_form, c->stream);
+                ks32_mac_hoist(c->ws.DS, ks->d_rs + key_off * (size_t)kb.S, U, perm, ident, cnt, R, guse, L, kb.S, n,
+                               kb.d_p32, kb.mac_form, c->stream, gs);
             }
             CHECK_LAUNCH();
             // the lift adds into a zeroed coefficient buffer; both components forward; c0 o perm_r joins
@@ -4231,8 +4261,9 @@ static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* 
             rb.dst = H; rb.dst_item_stride = 2 * Ln;
             rb.ppi = 2 * L; rb.prime_base = 0; rb.period = L;
             if (int e = run_ntt(c, rb, (long)cnt * R * 2 * L, false)) return e;
-            launch_hoist_c0(src, ks->d_perm, ks->d_ident, H, R, cnt, n, L, c->d_primes, c->stream);
+            launch_hoist_c0(src, perm, ident, H, R, cnt, n, L, c->d_primes, c->stream, gs);
             if (lt) launch_hoist_ptsum(H, c->pl_buf, dst, R, cnt, n, L, c->d_primes, c->stream);
+            if (prod) product(H);
             CHECK_LAUNCH();
             continue;
         }
@@ -4247,8 +4278,22 @@ static int hoist_core(exacto_ctx* c, const exacto_galois_keyset* ks, const u64* 
         {
             ProfScope pm(c, PK_RELIN_MAC, (u64)cnt * R * 2 * L,
                          8.0 * Ln * ((double)cnt * R * (guse + 1 + (lt ? 0 : 2)) + (double)R * guse * 4));
-            launch_hoist_mac(lt, src, c->ws.D, ks->d_keys, ks->d_keys_s, ks->d_perm, ks->d_ident,
-                             lt ? c->pl_buf : nullptr, dst, R, guse, cnt, n, L, c->d_primes, c->stream);
+            const u64* keys = guse > 0 ? ks->d_keys + key_off : nullptr;
+            const u64* keys_s = guse > 0 ? ks->d_keys_s + key_off : nullptr;
+            if (fused) {
+                const DbfvPlainArgs& p = *dv->prod;
+                DbfvHoistArgs a{};
+                a.ct = src; a.D = c->ws.D; a.keys = keys; a.keys_s = keys_s; a.perm = perm; a.ident = ident;
+                a.pl = p.pl; a.out = dst; a.items = cnt / gs;
+                a.R = R; a.guse = guse; a.d = gs; a.n = n; a.L = L;
+                a.flush = p.flush; a.accum = p.accum; a.live = p.live; a.fold = p.fold; a.primes = c->d_primes;
+                launch_dbfv_hoist_lt(a, c->stream);
+            } else {
+                u64* H = prod ? hs.as<u64>() + (size_t)li * h_words : dst;
+                launch_hoist_mac(lt, src, c->ws.D, keys, keys_s, perm, ident, lt ? c->pl_buf : nullptr, H, R, guse, cnt,
+                                 n, L, c->d_primes, c->stream, gs);
+                if (prod) product(H);
+            }
         }
         CHECK_LAUNCH();
     }
@@ -4856,6 +4901,12 @@ static int dbfv_plain_flush_products(const exacto_ctx* c) {
     return e >= 20 ? (1 << 20) : (1 << e) - 2;
 }
 
+extern "C" int exacto_ctx_set_dbfv_lt_fused(exacto_ctx* c, int on) {
+    if (!c) return invalid_param("null context");
+    c->dbfv_lt_fused = on != 0;
+    return 0;
+}
+
 extern "C" int exacto_dbfv_plain_limits(exacto_ctx* c, size_t* flush_products, size_t* chunk_terms) {
     if (!c) return invalid_param("null context");
     if (flush_products) *flush_products = (size_t)dbfv_plain_flush_products(c);
@@ -5073,6 +5124,212 @@ extern "C" int exacto_dbfv_plain_add(exacto_ctx* c, size_t d, const uint64_t* ct
 extern "C" int exacto_dbfv_plain_sub(exacto_ctx* c, size_t d, const uint64_t* ct, size_t polys, const uint64_t* pt,
                                      size_t pt_batch, uint64_t* out, size_t B) {
     return dbfv_plain_addsub_host(c, true, d, ct, polys, pt, pt_batch, out, B);
+}
+
+// ============================================================== dBFV hoisted rotations and linear transforms
+// The join of the hoisted rotations with the plaintext products ("dBFV linear transforms"):
+// out = reduce(sum_r W_r * rot_r(x)), bit for bit exacto_dbfv_plain_mul_sum over exacto_bfv_rotate_hoisted's
+// rotations of the limbs.  hoist_core runs it with the limbs of a ciphertext as one group.
+
+static int dbfv_hoist_rotate_check(exacto_ctx* c, const exacto_galois_keyset* ks, size_t d, const uint64_t* ct,
+                                   const uint64_t* out, size_t B) {
+    if (int e = check_ctx(c)) return e;
+    if (int e = hoist_check(c, ks)) return e;
+    if (d < 1) return invalid_param("num_digits must be >= 1");
+    if (d > 4096) return invalid_param("more than 4096 digits");
+    if (B == 0) return 0;
+    if (!ct || !out) return invalid_param("null argument");
+    return 0;
+}
+
+extern "C" int exacto_dbfv_rotate_hoisted_dev(exacto_ctx* c, const exacto_galois_keyset* ks, size_t d,
+                                              const uint64_t* ct, uint64_t* out, size_t B) {
+    if (int e = dbfv_hoist_rotate_check(c, ks, d, ct, out, B)) return e;
+    HoistDbfv dv;
+    dv.d = (int)d;
+    return hoist_core(c, ks, ct, nullptr, false, out, B * d, &dv);
+}
+
+extern "C" int exacto_dbfv_rotate_hoisted(exacto_ctx* c, const exacto_galois_keyset* ks, size_t d, const uint64_t* ct,
+                                          uint64_t* out, size_t B) {
+    if (int e = dbfv_hoist_rotate_check(c, ks, d, ct, out, B)) return e;
+    if (B == 0) return 0;
+    const size_t ctb = B * d * 2 * c->L * poly_bytes(c);
+    return host_call(c, {{ct, ctb}}, ctb * ks->R, out, [&](std::vector<u64*>& in, u64* o) {
+        return exacto_dbfv_rotate_hoisted_dev(c, ks, d, in[0], o, B);
+    });
+}
+
+// Lifted diagonals [R][d][L][n], resident on the device
+struct exacto_dbfv_diagonals {
+    int device = 0, n = 0, L = 0;
+    std::vector<u64> primes;
+    size_t R = 0, d = 0;
+    bool fused = false;      // dbfv_lt_fused_route of the context it was made on, when it was made
+    DevBuf<u64> d_pl;
+};
+
+// The route of a dBFV linear transform on this context: the fused kernel on the limb-wise key switch with
+// at most DP_MAX_D digits, else rotations into scratch and the plaintext-product kernel
+static bool dbfv_lt_fused_route(const exacto_ctx* c, size_t d) {
+    return c->dbfv_lt_fused && !hoist_k32(c) && d <= DP_MAX_D;
+}
+
+extern "C" void exacto_dbfv_diagonals_destroy(exacto_dbfv_diagonals* dg) {
+    if (!dg) return;
+    (void)hipSetDevice(dg->device);
+    delete dg;
+}
+
+extern "C" int exacto_dbfv_diagonals_info(const exacto_dbfv_diagonals* dg, size_t* R, size_t* d, int* fused) {
+    if (!dg) return invalid_param("null diagonals");
+    if (R) *R = dg->R;
+    if (d) *d = dg->d;
+    if (fused) *fused = dg->fused ? 1 : 0;
+    return 0;
+}
+
+extern "C" int exacto_dbfv_diagonals_create_dev(exacto_ctx* c, size_t d, size_t R, const uint64_t* pts,
+                                                exacto_dbfv_diagonals** out) {
+    if (int e = check_ctx(c)) return e;
+    if (!out || !pts) return invalid_param("null argument");
+    *out = nullptr;
+    if (d < 1) return invalid_param("num_digits must be >= 1");
+    if (d > 64) return invalid_param("plaintext product larger than 64 digits");
+    if (R == 0) return invalid_param("diagonals need at least one rotation");
+    if (R > 65535) return invalid_param("at most 65535 diagonals");
+    std::unique_ptr<exacto_dbfv_diagonals, void (*)(exacto_dbfv_diagonals*)> dg(new exacto_dbfv_diagonals,
+                                                                                exacto_dbfv_diagonals_destroy);
+    dg->device = c->device; dg->n = c->n; dg->L = c->L;
+    dg->primes.assign(c->primes.begin(), c->primes.begin() + c->L);
+    dg->R = R; dg->d = d;
+    dg->fused = dbfv_lt_fused_route(c, d);
+    if (int e = dg->d_pl.alloc(R * d * c->L * poly_bytes(c))) return e;
+    if (int e = lift_plain_rows(c, pts, (long)(R * d), dg->d_pl)) return e;
+    // the caller's pts may go once this returns
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *out = dg.release();
+    return 0;
+}
+
+extern "C" int exacto_dbfv_diagonals_create(exacto_ctx* c, size_t d, size_t R, const uint64_t* pts,
+                                            exacto_dbfv_diagonals** out) {
+    if (int e = check_ctx(c)) return e;
+    if (!out || !pts || d < 1 || d > 64 || R == 0 || R > 65535)   // nothing to stage: the device form's checks
+        return exacto_dbfv_diagonals_create_dev(c, d, R, pts, out);
+    const size_t bytes = R * d * poly_bytes(c);
+    DevBuf<u64> dp;
+    if (int e = dp.alloc(bytes)) return e;
+    if (int e = upload(c, dp, pts, bytes)) return e;
+    return exacto_dbfv_diagonals_create_dev(c, d, R, dp, out);
+}
+
+// The checks of exacto_dbfv_linear_transform[_prepared][_dev], in the header's order; exactly one of pts, dg
+static int dbfv_lt_check(exacto_ctx* c, const exacto_galois_keyset* ks, size_t d, uint64_t base, uint64_t plain,
+                         const uint64_t* ct, const uint64_t* pts, const exacto_dbfv_diagonals* dg, bool prepared,
+                         const uint64_t* out, size_t B, const uint32_t* depth_ct, bool dev) {
+    if (int e = check_ctx(c)) return e;
+    if (!ks) return invalid_param("null key set");
+    if (!ct || !out || (prepared ? !dg : !pts)) return invalid_param("null argument");
+    if (int e = hoist_check(c, ks)) return e;
+    if (int e = dbfv_params_check(d, base, plain)) return e;
+    if (d > 64) return invalid_param("plaintext product larger than 64 digits");
+    if (prepared) {
+        if (dg->n != c->n || dg->L != c->L || dg->device != c->device ||
+            !std::equal(dg->primes.begin(), dg->primes.end(), c->primes.begin()))
+            return invalid_param("diagonals were prepared on a context with other parameters");
+        if (dg->R != ks->R || dg->d != d)
+            return invalid_param("diagonals were prepared for " + std::to_string(dg->R) + " rotations of " +
+                                 std::to_string(dg->d) + " digits, not " + std::to_string(ks->R) + " of " +
+                                 std::to_string(d));
+    }
+    for (size_t i = 0; depth_ct && i < B; ++i)
+        if (depth_ct[i] + 1 > 1)
+            return fail(EXACTO_ERR_NOT_IMPLEMENTED, "not yet implemented: chained dBFV multiplication requires "
+                                                    "ciphertext-level lattice reduction (paper §4.6.2)");
+    if (dev && (((uintptr_t)ct | (uintptr_t)pts | (uintptr_t)out) & 15))
+        return invalid_param("dbfv linear transform: buffers must be 16-byte aligned");
+    const size_t n = (size_t)c->n, ctw = B * d * 2 * c->L * n;
+    if (ranges_overlap(out, ctw, ct, ctw) || (pts && ranges_overlap(out, ctw, pts, ks->R * d * n)))
+        return invalid_param("dbfv linear transform: the output must not overlap an input");
+    return 0;
+}
+
+static int dbfv_lt_dev(exacto_ctx* c, const exacto_galois_keyset* ks, size_t d, uint64_t base, uint64_t plain,
+                       const uint64_t* ct, const uint64_t* pts, const exacto_dbfv_diagonals* dg, bool prepared,
+                       uint64_t* out, size_t B, const uint32_t* depth_ct, uint32_t* depth_out) {
+    if (int e = dbfv_lt_check(c, ks, d, base, plain, ct, pts, dg, prepared, out, B, depth_ct, true)) return e;
+    if (B == 0) return 0;
+    unsigned live = 0;
+    int E = 0;
+    if (int e = dbfv_plain_tables(c, d, base, plain, &live, &E)) return e;
+    const size_t n = (size_t)c->n, Ln = (size_t)c->L * n, R = ks->R;
+    DbfvPlainArgs a{};
+    a.d = (int)d; a.polys = 2; a.n = c->n; a.L = c->L;
+    a.flush = dbfv_plain_flush_products(c);
+    a.live = live;
+    a.fold = c->d_dp.get() + 2;
+    a.pairs = reinterpret_cast<const DpPair*>(c->d_dp.get() + 2);
+    a.E = E;
+    a.primes = c->d_primes;
+    a.pl_term_stride = (long)(d * Ln);
+    a.pl_item_stride = 0;
+    HoistDbfv dv;
+    dv.d = (int)d;
+    dv.prod = &a;
+    dv.fused = dbfv_lt_fused_route(c, d);
+    // raw diagonals: plain_terms rotations at a time through pl_buf, a later group adding into out
+    const size_t Rc = prepared ? R : std::min(R, c->plain_terms);
+    if (!prepared)
+        if (int e = pl_scratch(c, Rc * d * Ln)) return e;
+    for (size_t r0 = 0; r0 < R; r0 += Rc) {
+        const size_t rc = std::min(Rc, R - r0);
+        if (!prepared)
+            if (int e = lift_plain_rows(c, pts + r0 * d * n, (long)(rc * d), c->pl_buf)) return e;
+        a.pl = prepared ? dg->d_pl.get() : c->pl_buf.get();
+        a.accum = r0 != 0;
+        dv.r0 = r0; dv.rc = rc;
+        if (int e = hoist_core(c, ks, ct, nullptr, false, out, B * d, &dv)) return e;
+    }
+    if (depth_out)
+        for (size_t i = 0; i < B; ++i) depth_out[i] = 1;
+    return 0;
+}
+
+extern "C" int exacto_dbfv_linear_transform_dev(exacto_ctx* c, const exacto_galois_keyset* ks, size_t d, uint64_t base,
+                                                uint64_t plain, const uint64_t* ct, const uint64_t* pts, uint64_t* out,
+                                                size_t B, const uint32_t* depth_ct, uint32_t* depth_out) {
+    return dbfv_lt_dev(c, ks, d, base, plain, ct, pts, nullptr, false, out, B, depth_ct, depth_out);
+}
+
+extern "C" int exacto_dbfv_linear_transform_prepared_dev(exacto_ctx* c, const exacto_galois_keyset* ks, size_t d,
+                                                         uint64_t base, uint64_t plain, const uint64_t* ct,
+                                                         const exacto_dbfv_diagonals* dg, uint64_t* out, size_t B,
+                                                         const uint32_t* depth_ct, uint32_t* depth_out) {
+    return dbfv_lt_dev(c, ks, d, base, plain, ct, nullptr, dg, true, out, B, depth_ct, depth_out);
+}
+
+extern "C" int exacto_dbfv_linear_transform(exacto_ctx* c, const exacto_galois_keyset* ks, size_t d, uint64_t base,
+                                            uint64_t plain, const uint64_t* ct, const uint64_t* pts, uint64_t* out,
+                                            size_t B, const uint32_t* depth_ct, uint32_t* depth_out) {
+    if (int e = dbfv_lt_check(c, ks, d, base, plain, ct, pts, nullptr, false, out, B, depth_ct, false)) return e;
+    if (B == 0) return 0;
+    const size_t ctb = B * d * 2 * c->L * poly_bytes(c);
+    return host_call(c, {{ct, ctb}, {pts, ks->R * d * poly_bytes(c)}}, ctb, out, [&](std::vector<u64*>& in, u64* o) {
+        return exacto_dbfv_linear_transform_dev(c, ks, d, base, plain, in[0], in[1], o, B, depth_ct, depth_out);
+    });
+}
+
+extern "C" int exacto_dbfv_linear_transform_prepared(exacto_ctx* c, const exacto_galois_keyset* ks, size_t d,
+                                                     uint64_t base, uint64_t plain, const uint64_t* ct,
+                                                     const exacto_dbfv_diagonals* dg, uint64_t* out, size_t B,
+                                                     const uint32_t* depth_ct, uint32_t* depth_out) {
+    if (int e = dbfv_lt_check(c, ks, d, base, plain, ct, nullptr, dg, true, out, B, depth_ct, false)) return e;
+    if (B == 0) return 0;
+    const size_t ctb = B * d * 2 * c->L * poly_bytes(c);
+    return host_call(c, {{ct, ctb}}, ctb, out, [&](std::vector<u64*>& in, u64* o) {
+        return exacto_dbfv_linear_transform_prepared_dev(c, ks, d, base, plain, in[0], dg, o, B, depth_ct, depth_out);
+    });
 }
 
 // ============================================================== diagnostics

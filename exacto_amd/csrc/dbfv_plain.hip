@@ -23,7 +23,7 @@
 // The fold of the high limbs (rep[m - d][i] wide[m], m >= d) uses the digits rep mod q_l from the
 // host: the high sums are reduced to canonical residues first, the low sums too, and the at most d - 1
 // products of the fold join one low residue in the accumulator (d <= N), reduced once more.
-#include "exacto_internal.hpp"
+#include "dbfv_acc.hpp"
 
 namespace exacto {
 
@@ -36,12 +36,8 @@ struct DpAcc {   // the two positions' 128-bit sums
     u128 x, y;
 };
 
-// hi:lo (any 128-bit value) mod q; r64 = 2^64 mod q
-__device__ __forceinline__ u64 pl_red(u128 v, const PrimeConst& P, u64 r64) {
-    const u64 h = reduce64((u64)(v >> 64), P.q, P.mu64);
-    const u64 l = reduce64((u64)v, P.q, P.mu64);
-    return add_mod(mul_mod(h, r64, P), l, P.q);
-}
+__device__ __forceinline__ u128& dp_x(DpAcc& a) { return a.x; }
+__device__ __forceinline__ u128& dp_y(DpAcc& a) { return a.y; }
 
 struct DpRow {   // a thread's row and position
     long item;
@@ -84,7 +80,7 @@ dbfv_plain_mul_kernel(const u64* __restrict__ cts, long ct_item_stride, long ct_
     if (!w.ok) return;
     const PrimeConst& P = primes[w.l];
     const u64 q = P.q;
-    const u64 r64 = add_mod(reduce64(~(u64)0, q, P.mu64), 1, q);
+    const u64 r64 = pl_r64(P);
     const long limb_stride = (long)rpi * n, Ln = (long)L * n;
     const u64* cp = cts + w.item * ct_item_stride + (long)w.r * n + w.j;
     const u64* pp = pl + w.item * pl_item_stride + (long)w.l * n + w.j;
@@ -133,7 +129,7 @@ dbfv_plain_mul_kernel(const u64* __restrict__ cts, long ct_item_stride, long ct_
         // by wide limb, so that limb m waits for the first m + 1 digits of either operand only
 #pragma unroll
         for (int m = 0; m < W; ++m) {
-            if (m < D || (live >> (m - D) & 1)) {
+            if (pl_live<D>(live, m)) {
 #pragma unroll
                 for (int i = 0; i < D; ++i) {
                     const int j = m - i;
@@ -146,11 +142,8 @@ dbfv_plain_mul_kernel(const u64* __restrict__ cts, long ct_item_stride, long ct_
         }
         if (++since == flush_terms && k + 1 < K) {
             since = 0;
-#pragma unroll
-            for (int m = 0; m < W; ++m) {
-                acc[m].x = pl_red(acc[m].x, P, r64);
-                acc[m].y = pl_red(acc[m].y, P, r64);
-            }
+            pl_red_all<W>(acc, P, r64, dp_x);
+            pl_red_all<W>(acc, P, r64, dp_y);
         }
         if (PF) {
 #pragma unroll
@@ -160,23 +153,10 @@ dbfv_plain_mul_kernel(const u64* __restrict__ cts, long ct_item_stride, long ct_
             }
         }
     }
-    if (HI) {
-#pragma unroll
-        for (int m = 0; m < W; ++m) {
-            acc[m].x = pl_red(acc[m].x, P, r64);
-            acc[m].y = pl_red(acc[m].y, P, r64);
-        }
+    if constexpr (HI) {
         const u64* f = fold + (long)w.l * (D - 1) * D;
-#pragma unroll
-        for (int m = D; m < W; ++m)
-            if (live >> (m - D) & 1) {
-#pragma unroll
-                for (int i = 0; i < D; ++i) {
-                    const u64 s = f[(m - D) * D + i];
-                    acc[i].x += (u128)s * (u64)acc[m].x;
-                    acc[i].y += (u128)s * (u64)acc[m].y;
-                }
-            }
+        pl_fold<D>(acc, live, f, P, r64, dp_x);
+        pl_fold<D>(acc, live, f, P, r64, dp_y);
     }
     u64* dst = out + (w.item * D * rpi + w.r) * n + w.j;
 #pragma unroll
@@ -206,7 +186,7 @@ dbfv_plain_mul_list_kernel(const u64* __restrict__ cts, long ct_item_stride, lon
     if (!w.ok) return;
     const PrimeConst& P = primes[w.l];
     const u64 q = P.q;
-    const u64 r64 = add_mod(reduce64(~(u64)0, q, P.mu64), 1, q);
+    const u64 r64 = pl_r64(P);
     const long limb_stride = (long)rpi * n, Ln = (long)L * n;
     const u64* cp = cts + w.item * ct_item_stride + (long)w.r * n + w.j;
     const u64* pp = pl + w.item * pl_item_stride + (long)w.l * n + w.j;

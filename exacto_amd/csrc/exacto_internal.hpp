@@ -146,11 +146,16 @@ void ks32_key_norms(const u64* K, u64* out, long rows, int L, int n, const Prime
 // U [items][2L][S][n] = sum_g DS (.) RS
 void ks32_mac(const uint32_t* DS, const uint32_t* RS, uint32_t* U, int items, int G, int L, int S, int n,
               const Prime32* primes, int mac_form, hipStream_t st);
-// hoisted rotations: U [items][R][2L][S][n] = sum_g (DS_g o perm_r) (.) RSK [r][g], perm [R][n] storage
-// positions, ident [R] non-zero for the identity element (no key read, zero sums); R <= 65535
+// Where the hoisted rotation kernels put output (item, r): [item / gs][R][item % gs].  gs = 1 is [item][R];
+// gs = d groups the d limbs of a dBFV ciphertext under each rotation (items a multiple of d).
+__host__ __device__ __forceinline__ long hoist_out_index(long item, int r, int R, int gs) {
+    return ((item / gs) * R + r) * gs + item % gs;
+}
+// hoisted rotations: U [hoist_out_index(item, r, R, gs)][2L][S][n] = sum_g (DS_g o perm_r) (.) RSK [r][g], perm
+// [R][n] storage positions, ident [R] non-zero for the identity element (no key read, zero sums); R <= 65535
 void ks32_mac_hoist(const uint32_t* DS, const uint32_t* RSK, uint32_t* U, const uint32_t* perm,
                     const unsigned char* ident, int items, int R, int G, int L, int S, int n, const Prime32* primes,
-                    int mac_form, hipStream_t st);
+                    int mac_form, hipStream_t st, int gs = 1);
 // R[item][c][l] += centred lift of INTT(U[item][c][l][.]) mod q_l (every q_l = 2^60 - d, d < 2^24)
 // fpc: the lift by a rounded float sum (ks32_dev.hpp ks32_fpc_one; taken when S <= 3 or the primes are
 // below 2^32 / 3, and the caller checked the basis' fpc_max)
@@ -287,13 +292,14 @@ void launch_relin_mac(const u64* base, long base_stride, const u64* D, const u64
 
 // ---- hoisted rotations (hoist.hip): ct [items][2][L][n], D [items][guse][L][n] the transformed digits of c1,
 // keys / keys_s [R][guse][2][L][n] with Shoup companions, perm [R][n], ident [R]
-// lt: out [items][2][L][n] = sum_r pts[r] (.) rotation r (pts [R][L][n]); otherwise out [items][R][2][L][n]
+// lt: out [items][2][L][n] = sum_r pts[r] (.) rotation r (pts [R][L][n]); otherwise out
+// [hoist_out_index(item, r, R, gs)][2][L][n]
 void launch_hoist_mac(bool lt, const u64* ct, const u64* D, const u64* keys, const u64* keys_s, const uint32_t* perm,
                       const unsigned char* ident, const u64* pts, u64* out, int R, int guse, int items, int n, int L,
-                      const PrimeConst* primes, hipStream_t s);
-// H [items][R][2][L][n] += (c0 o perm_r, 0) (identity: += the input ciphertext)
+                      const PrimeConst* primes, hipStream_t s, int gs = 1);
+// H [hoist_out_index(item, r, R, gs)][2][L][n] += (c0 o perm_r, 0) (identity: += the input ciphertext)
 void launch_hoist_c0(const u64* ct, const uint32_t* perm, const unsigned char* ident, u64* H, int R, int items, int n,
-                     int L, const PrimeConst* primes, hipStream_t s);
+                     int L, const PrimeConst* primes, hipStream_t s, int gs = 1);
 // out [items][2][L][n] = sum_r pts[r] (.) H[item][r]
 void launch_hoist_ptsum(const u64* H, const u64* pts, u64* out, int R, int items, int n, int L,
                         const PrimeConst* primes, hipStream_t s);
@@ -397,6 +403,25 @@ struct DbfvPlainArgs {
 };
 // every buffer 16-byte aligned, out disjoint from the inputs
 void launch_dbfv_plain_mul(const DbfvPlainArgs& a, hipStream_t s);
+
+// ---- dBFV linear transforms on the limb-wise key-switch path (dbfv_hoist.hip), d <= DP_MAX_D ----
+#define DH_NC2_MAX_W 7   // wide limbs up to which a thread keeps both components' sums (above: one component)
+struct DbfvHoistArgs {
+    const u64* ct;               // [items][d][2][L][n]
+    const u64* D;                // [items * d][guse][L][n], the transformed digits of every limb's c1
+    const u64 *keys, *keys_s;    // [R][guse][2][L][n] and Shoup companions
+    const uint32_t* perm;        // [R][n]
+    const unsigned char* ident;  // [R]
+    const u64* pl;               // lifted diagonals [R][d][L][n]
+    u64* out;                    // [items][d][2][L][n]
+    long items;
+    int R, guse, d, n, L;
+    int flush, accum;            // as DbfvPlainArgs
+    unsigned live;
+    const u64* fold;
+    const PrimeConst* primes;
+};
+void launch_dbfv_hoist_lt(const DbfvHoistArgs& a, hipStream_t s);
 
 // ---- plaintext-ciphertext operations (plain.hip) ----
 enum { PLAIN_MUL = 0, PLAIN_ADD = 1, PLAIN_SUB = 2 };

@@ -13,6 +13,8 @@
 //   hoist_c0_kernel         : the 31-bit path's last step, H[it][r] += (c0 o perm_r, 0) in the NTT domain
 //   hoist_ptsum_kernel      : the 31-bit path's linear transform, out[it] = sum_r pt_r (.) H[it][r]
 // A rotation by the identity element (ident[r] != 0) reads no key: its output is the input ciphertext.
+// The rotation kernels place output (item, r) at hoist_out_index(item, r, R, gs): gs = 1 is [item][R]; gs = d
+// makes the d limbs of a dBFV ciphertext one group, [item / d][R][item % d] (items a multiple of d).
 #include "exacto_internal.hpp"
 
 namespace exacto {
@@ -28,7 +30,7 @@ __global__ void __launch_bounds__(HO_TPB)
 hoist_mac_kernel(const u64* __restrict__ ct, const u64* __restrict__ D, const u64* __restrict__ keys,
                  const u64* __restrict__ keys_s, const uint32_t* __restrict__ perm,
                  const unsigned char* __restrict__ ident, const u64* __restrict__ pts, u64* __restrict__ out, int R,
-                 int guse, int items, int nblk, int n, int L, const PrimeConst* __restrict__ primes) {
+                 int guse, int items, int nblk, int n, int L, const PrimeConst* __restrict__ primes, int gs) {
     const long Ln = (long)L * n;
     const unsigned it = blockIdx.x % (unsigned)items;
     const unsigned rest = blockIdx.x / (unsigned)items;
@@ -84,7 +86,7 @@ hoist_mac_kernel(const u64* __restrict__ ct, const u64* __restrict__ D, const u6
             s0 = add_mod(s0, mul_mod(a0, m, P), q);
             s1 = add_mod(s1, mul_mod(a1, m, P), q);
         } else {
-            u64* op = out + ((long)it * R + r) * 2 * Ln;
+            u64* op = out + hoist_out_index(it, r, R, gs) * 2 * Ln;
             op[coef] = a0;
             op[Ln + coef] = a1;
         }
@@ -108,7 +110,7 @@ __global__ void __launch_bounds__(HO_TPB)
 hoist_mac_lds_kernel(const u64* __restrict__ ct, const u64* __restrict__ D, const u64* __restrict__ keys,
                      const u64* __restrict__ keys_s, const uint32_t* __restrict__ perm,
                      const unsigned char* __restrict__ ident, u64* __restrict__ out, int R, int guse, int items, int n,
-                     int L, const PrimeConst* __restrict__ primes) {
+                     int L, const PrimeConst* __restrict__ primes, int gs) {
     extern __shared__ u64 kst[];  // [guse][4][HO_LS]: w0, ws0, w1, ws1
     const long Ln = (long)L * n;
     const long c0 = (long)blockIdx.x * HO_LS;  // first position (flat limb * n + j)
@@ -119,7 +121,7 @@ hoist_mac_lds_kernel(const u64* __restrict__ ct, const u64* __restrict__ D, cons
     if (ident[r]) {   // block-uniform
         for (int it = blockIdx.y * HO_IG + wave; it < it_end; it += HO_TPB / HO_LS) {
             const u64* cp = ct + (long)it * 2 * Ln;
-            u64* op = out + ((long)it * R + r) * 2 * Ln;
+            u64* op = out + hoist_out_index(it, r, R, gs) * 2 * Ln;
             op[coef] = cp[coef];
             op[Ln + coef] = cp[Ln + coef];
         }
@@ -156,7 +158,7 @@ hoist_mac_lds_kernel(const u64* __restrict__ ct, const u64* __restrict__ D, cons
                 }
             }
         }
-        u64* op = out + ((long)it * R + r) * 2 * Ln;
+        u64* op = out + hoist_out_index(it, r, R, gs) * 2 * Ln;
         op[coef] = a0 >= q ? a0 - q : a0;
         op[Ln + coef] = a1 >= q ? a1 - q : a1;
     }
@@ -164,36 +166,38 @@ hoist_mac_lds_kernel(const u64* __restrict__ ct, const u64* __restrict__ D, cons
 
 void launch_hoist_mac(bool lt, const u64* ct, const u64* D, const u64* keys, const u64* keys_s, const uint32_t* perm,
                       const unsigned char* ident, const u64* pts, u64* out, int R, int guse, int items, int n, int L,
-                      const PrimeConst* primes, hipStream_t s) {
+                      const PrimeConst* primes, hipStream_t s, int gs) {
     if (items <= 0 || R <= 0) return;
     const long Ln = (long)L * n;
     if (!lt && guse > 0 && guse <= HO_GMAX && Ln % HO_LS == 0 && R <= 65535) {
         const dim3 grid((unsigned)(Ln / HO_LS), (unsigned)((items + HO_IG - 1) / HO_IG), (unsigned)R);
         EXACTO_LAUNCH(hoist_mac_lds_kernel, grid, dim3(HO_TPB), (size_t)guse * 4 * HO_LS * sizeof(u64), s, ct, D, keys,
-                      keys_s, perm, ident, out, R, guse, items, n, L, primes);
+                      keys_s, perm, ident, out, R, guse, items, n, L, primes, gs);
         return;
     }
     const int nblk = (int)((Ln + HO_TPB - 1) / HO_TPB);
     const long blocks = (long)items * nblk * (lt ? 1 : R);
     if (lt)
         EXACTO_LAUNCH(hoist_mac_kernel<true>, dim3((unsigned)blocks), dim3(HO_TPB), 0, s, ct, D, keys, keys_s, perm,
-                      ident, pts, out, R, guse, items, nblk, n, L, primes);
+                      ident, pts, out, R, guse, items, nblk, n, L, primes, gs);
     else
         EXACTO_LAUNCH(hoist_mac_kernel<false>, dim3((unsigned)blocks), dim3(HO_TPB), 0, s, ct, D, keys, keys_s, perm,
-                      ident, pts, out, R, guse, items, nblk, n, L, primes);
+                      ident, pts, out, R, guse, items, nblk, n, L, primes, gs);
 }
 
 // H [items][R][2][L][n] (the key-switched sums, NTT domain) += (c0 o perm_r, 0); the identity element's
 // sums are zero and it takes both components of the input as they are.
 __global__ void __launch_bounds__(HO_TPB)
 hoist_c0_kernel(const u64* __restrict__ ct, const uint32_t* __restrict__ perm, const unsigned char* __restrict__ ident,
-                u64* __restrict__ H, int R, int nblk, int n, int L, const PrimeConst* __restrict__ primes) {
+                u64* __restrict__ H, int R, int nblk, int n, int L, const PrimeConst* __restrict__ primes,
+                int gs) {
     const long Ln = (long)L * n;
-    const unsigned ir = blockIdx.x / (unsigned)nblk;          // item * R + r
+    const unsigned ir = blockIdx.x / (unsigned)nblk;          // H's index: hoist_out_index(item, r, R, gs)
     const long coef = (long)(blockIdx.x - ir * (unsigned)nblk) * HO_TPB + threadIdx.x;
     if (coef >= Ln) return;
-    const unsigned it = ir / (unsigned)R;
-    const int r = (int)(ir - it * (unsigned)R);
+    const unsigned grp = ir / ((unsigned)R * gs), in_grp = ir - grp * ((unsigned)R * gs);
+    const int r = (int)(in_grp / (unsigned)gs);
+    const unsigned it = grp * gs + (in_grp - (unsigned)r * gs);
     const int l = (int)(coef / n);
     const int j = (int)(coef - (long)l * n);
     const u64 q = primes[l].q;
@@ -208,11 +212,11 @@ hoist_c0_kernel(const u64* __restrict__ ct, const uint32_t* __restrict__ perm, c
 }
 
 void launch_hoist_c0(const u64* ct, const uint32_t* perm, const unsigned char* ident, u64* H, int R, int items, int n,
-                     int L, const PrimeConst* primes, hipStream_t s) {
+                     int L, const PrimeConst* primes, hipStream_t s, int gs) {
     if (items <= 0 || R <= 0) return;
     const int nblk = (int)(((long)L * n + HO_TPB - 1) / HO_TPB);
     EXACTO_LAUNCH(hoist_c0_kernel, dim3((unsigned)((long)items * R * nblk)), dim3(HO_TPB), 0, s, ct, perm, ident, H, R,
-                  nblk, n, L, primes);
+                  nblk, n, L, primes, gs);
 }
 
 // out[it][c][l][j] = sum_r pts[r][l][j] H[it][r][c][l][j] mod q_l: one streaming pass over H

@@ -206,13 +206,13 @@ ks32_mac_kernel(const int* __restrict__ DS, const int* __restrict__ RS, uint32_t
 // The hoisted form of ks32_mac_kernel (hoist.hip): rotation r = blockIdx.z of every item reads the digit
 // residues of the item's own c1 through perm_r (NTT(sigma_r(d_g)) = DS_g o perm_r, a 4-byte gather inside
 // one n-word row that the R rotations of an item share in L2) and key slice r of RSK [R][G][CL][S][n],
-// staged in LDS as above.  U [item][R][cl][s][n].  An identity rotation (ident[r]) reads no key and
+// staged in LDS as above.  U [hoist_out_index(item, r, R, gs)][cl][s][n] ([item][R] at gs = 1).  An identity rotation (ident[r]) reads no key and
 // writes zero sums.
 template <int CLB, int NW, int RUN, bool LZ = false>
 __global__ void __launch_bounds__(NW * 64)
 ks32_mac_hoist_kernel(const int* __restrict__ DS, const int* __restrict__ RSK, uint32_t* __restrict__ U,
                       const uint32_t* __restrict__ perm, const unsigned char* __restrict__ ident, int G, int CL, int S,
-                      int items, int n, const Prime32* __restrict__ primes) {
+                      int items, int n, const Prime32* __restrict__ primes, int gs) {
     extern __shared__ int kl[];                // [g][cl - cl0][lane]
     constexpr int IG = 4 * NW;                 // items per block
     const int lane = threadIdx.x & (KS_LS - 1);
@@ -228,7 +228,7 @@ ks32_mac_hoist_kernel(const int* __restrict__ DS, const int* __restrict__ RSK, u
     if (ident[r]) {
         for (int it = blockIdx.y * IG + wave; it < it_end; it += NW)
 #pragma unroll
-            for (int c = 0; c < CLB; ++c) U[((((long)it * R + r) * CL + cl0 + c) * S + s) * n + j] = 0;
+            for (int c = 0; c < CLB; ++c) U[((hoist_out_index(it, r, R, gs) * CL + cl0 + c) * S + s) * n + j] = 0;
         return;
     }
     const int* RS = RSK + (long)r * G * CL * S * n;
@@ -262,7 +262,7 @@ ks32_mac_hoist_kernel(const int* __restrict__ DS, const int* __restrict__ RSK, u
         }
 #pragma unroll
         for (int c = 0; c < CLB; ++c)
-            U[((((long)it * R + r) * CL + cl0 + c) * S + s) * n + j] = LZ ? red_s64_lz(acc[c], P) : red_s64(acc[c], P);
+            U[((hoist_out_index(it, r, R, gs) * CL + cl0 + c) * S + s) * n + j] = LZ ? red_s64_lz(acc[c], P) : red_s64(acc[c], P);
     }
 }
 
@@ -460,7 +460,7 @@ void ks32_mac(const uint32_t* DS, const uint32_t* RS, uint32_t* U, int items, in
 
 void ks32_mac_hoist(const uint32_t* DS, const uint32_t* RSK, uint32_t* U, const uint32_t* perm,
                     const unsigned char* ident, int items, int R, int G, int L, int S, int n, const Prime32* primes,
-                    int mac_form, hipStream_t st) {
+                    int mac_form, hipStream_t st, int gs) {
     if (items <= 0 || R <= 0) return;
     const int CL = 2 * L;
     // the block shape of ks32_mac, with the rotation in grid.z
@@ -471,7 +471,7 @@ void ks32_mac_hoist(const uint32_t* DS, const uint32_t* RSK, uint32_t* U, const 
     const dim3 grid((unsigned)((n / KS_LS) * S * (CL / CLB)), (unsigned)((items + 4 * NW - 1) / (4 * NW)), (unsigned)R);
     const int* ds = reinterpret_cast<const int*>(DS);
     const int* rs = reinterpret_cast<const int*>(RSK);
-#define MAC_(C_, W_, R_, Z_) EXACTO_LAUNCH((ks32_mac_hoist_kernel<C_, W_, R_, Z_>), grid, dim3(W_ * 64), lds, st, ds, rs, U, perm, ident, G, CL, S, items, n, primes)
+#define MAC_(C_, W_, R_, Z_) EXACTO_LAUNCH((ks32_mac_hoist_kernel<C_, W_, R_, Z_>), grid, dim3(W_ * 64), lds, st, ds, rs, U, perm, ident, G, CL, S, items, n, primes, gs)
 #define MAC(C_)                                                  \
     do {                                                         \
         if (mac_form == 2) { if (NW == 8) MAC_(C_, 8, 12, true); else MAC_(C_, 4, 12, true); } \

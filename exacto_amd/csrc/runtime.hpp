@@ -259,6 +259,10 @@ struct exacto_ctx {
     // products' tensors in the auxiliary primes (run_mul, dbfv_mul_core); psum_max = the largest
     // product count m with m (p n Q + 2) < P, so that the summed rounding stays liftable from P
     bool psum_env = true;
+    // dBFV linear transforms on the limb-wise key switch: the staged route (rotations into scratch, then the
+    // plaintext-product kernel) unless exacto_ctx_set_dbfv_lt_fused(ctx, 1) selects dbfv_hoist.hip's fused
+    // kernel, which measured half as fast; the switch is for tests and measurements
+    bool dbfv_lt_fused = false;
     bool square_hook = true;     // eval_poly's baby steps x^(i/2) x^(i/2) on the square path (exacto_ctx_set_square_hook)
     int psum_max = 0;
     int psum_fp_max = 0;         // ... and with |sum| < P / 4, the rounded-float CRT over P (kernels.hip fpc_lift)

@@ -1523,6 +1523,97 @@ inline DbfvCiphertext dbfv_batch_plain_mul(const DbfvCiphertext& ct, const SlotV
     return dbfv_plain_mul(ct, dbfv_batch_encode(values, ct.params));
 }
 
+// ---- dBFV hoisted rotations and slot linear transforms with wide public diagonals (exacto_dbfv_linear_transform*,
+// no reference function): reduce(sum_r W_r * rot_r(x)), bit for bit dbfv_plain_mul_sum over the rotations
+// bfv_rotate_hoisted makes of the limbs.
+// out[r] = the set's automorphism r of ct, limb by limb on the shared gadget digits of each limb's c1
+inline std::vector<DbfvCiphertext> dbfv_rotate_hoisted(const DbfvCiphertext& ct, const GaloisKeySet& ks) {
+    const DbfvParams& dp = *ct.params;
+    const size_t d = ct.num_limbs(), R = ks.size(), per = d * 2 * detail::limb_words(dp);
+    if (detail::dbfv_polys(ct) != 2) throw ExactoError(EXACTO_ERR_INVALID_PARAM, "invalid parameter: automorphism requires degree-1 ciphertext");
+    auto flat = detail::flatten_dbfv(ct);
+    std::vector<uint64_t> out(R * per);
+    detail::check(exacto_dbfv_rotate_hoisted(dp.bfv_params->ctx(), ks.handle(), d, flat.data(), out.data(), 1));
+    std::vector<DbfvCiphertext> res;
+    for (size_t r = 0; r < R; ++r) {
+        std::vector<uint64_t> one(out.begin() + (long)(r * per), out.begin() + (long)((r + 1) * per));
+        res.push_back(detail::make_dbfv(one, d, 2, ct.degree, ct.mul_depth, ct.params));
+    }
+    return res;
+}
+// Both rows of the wide slots left by every steps[r] at once; ks holds the elements
+// galois_element_rotate_rows(n, steps[r]) in this order
+inline std::vector<DbfvCiphertext> dbfv_rotate_rows_many(const DbfvCiphertext& ct, const std::vector<int64_t>& steps,
+                                                         const GaloisKeySet& ks) {
+    const size_t n = ct.params->bfv_params->ring_degree;
+    bool same = steps.size() == ks.size();
+    for (size_t r = 0; same && r < steps.size(); ++r)
+        same = ks.elements()[r] % (2 * n) == galois_element_rotate_rows(n, steps[r]);
+    if (!same) throw ExactoError(1, "invalid parameter: the key set does not hold the elements of these steps in this order");
+    return dbfv_rotate_hoisted(ct, ks);
+}
+
+// Wide public diagonals lifted once (exacto_dbfv_diagonals_create): one DbfvSlotPlain per element of the key
+// set they will be used with.  Keeps its parameters (and with them the context) alive.
+class DbfvDiagonals {
+public:
+    DbfvDiagonals(const DbfvParamsPtr& params, const std::vector<DbfvSlotPlain>& pts) : params_(params), R_(pts.size()) {
+        std::vector<uint64_t> flat;
+        for (auto& p : pts) detail::append_plain(flat, p, *params);
+        detail::check(exacto_dbfv_diagonals_create(params->bfv_params->ctx(), params->num_digits, pts.size(),
+                                                   flat.empty() ? nullptr : flat.data(), &h_));
+    }
+    DbfvDiagonals(const DbfvDiagonals&) = delete;
+    DbfvDiagonals& operator=(const DbfvDiagonals&) = delete;
+    DbfvDiagonals(DbfvDiagonals&& o) noexcept : params_(std::move(o.params_)), R_(o.R_), h_(o.h_) { o.h_ = nullptr; }
+    ~DbfvDiagonals() { exacto_dbfv_diagonals_destroy(h_); }
+    const exacto_dbfv_diagonals* handle() const { return h_; }
+    size_t size() const { return R_; }
+    const DbfvParamsPtr& params() const { return params_; }
+    // the route a transform takes on this context: the fused kernel, or rotations staged for the product kernel
+    bool fused() const {
+        int f = 0;
+        detail::check(exacto_dbfv_diagonals_info(h_, nullptr, nullptr, &f));
+        return f != 0;
+    }
+
+private:
+    DbfvParamsPtr params_;
+    size_t R_ = 0;
+    exacto_dbfv_diagonals* h_ = nullptr;
+};
+
+// reduce(sum_r pts[r] * (automorphism r of ct)): raw diagonals (lifted on every call) or prepared ones
+inline DbfvCiphertext dbfv_linear_transform(const DbfvCiphertext& ct, const GaloisKeySet& ks,
+                                            const std::vector<DbfvSlotPlain>& pts) {
+    const DbfvParams& dp = *ct.params;
+    const size_t d = dp.num_digits;
+    if (ct.num_limbs() != d) throw ExactoError(1, "invalid parameter: multiplication requires d-limb ciphertexts");
+    if (detail::dbfv_polys(ct) != 2) throw ExactoError(EXACTO_ERR_INVALID_PARAM, "invalid parameter: automorphism requires degree-1 ciphertext");
+    if (pts.size() != ks.size()) throw ExactoError(EXACTO_ERR_INVALID_PARAM, "invalid parameter: one plaintext per element of the key set");
+    auto flat = detail::flatten_dbfv(ct);
+    std::vector<uint64_t> fp, out(flat.size());
+    for (auto& p : pts) detail::append_plain(fp, p, dp);
+    const uint32_t depth = (uint32_t)ct.mul_depth;
+    uint32_t dout = 0;
+    detail::check(exacto_dbfv_linear_transform(dp.bfv_params->ctx(), ks.handle(), d, dp.base, dp.plain_modulus,
+                                               flat.data(), fp.data(), out.data(), 1, &depth, &dout));
+    return detail::make_dbfv(out, d, 2, d, dout, ct.params);
+}
+inline DbfvCiphertext dbfv_linear_transform(const DbfvCiphertext& ct, const GaloisKeySet& ks, const DbfvDiagonals& dg) {
+    const DbfvParams& dp = *ct.params;
+    const size_t d = dp.num_digits;
+    if (ct.num_limbs() != d) throw ExactoError(1, "invalid parameter: multiplication requires d-limb ciphertexts");
+    if (detail::dbfv_polys(ct) != 2) throw ExactoError(EXACTO_ERR_INVALID_PARAM, "invalid parameter: automorphism requires degree-1 ciphertext");
+    auto flat = detail::flatten_dbfv(ct);
+    std::vector<uint64_t> out(flat.size());
+    const uint32_t depth = (uint32_t)ct.mul_depth;
+    uint32_t dout = 0;
+    detail::check(exacto_dbfv_linear_transform_prepared(dp.bfv_params->ctx(), ks.handle(), d, dp.base, dp.plain_modulus,
+                                                        flat.data(), dg.handle(), out.data(), 1, &depth, &dout));
+    return detail::make_dbfv(out, d, 2, d, dout, ct.params);
+}
+
 // dbfv_div_by_base (src/dbfv/advanced.rs:36-93): the result carries new DbfvParams with p / base.
 inline DbfvCiphertext dbfv_div_by_base(const DbfvCiphertext& ct) {
     const DbfvParams& dp = *ct.params;

@@ -766,6 +766,72 @@ int exacto_dbfv_plain_sub_dev(exacto_ctx* ctx, size_t d, const uint64_t* ct, siz
 int exacto_ctx_set_plain_terms(exacto_ctx* ctx, size_t terms);
 int exacto_dbfv_plain_limits(exacto_ctx* ctx, size_t* flush_products, size_t* chunk_terms);
 
+/* ---- Slot linear transforms on dBFV ciphertexts with public wide diagonals ----
+ * The join of the hoisted rotations with the dBFV plaintext products: a public matrix over Z_p (p up to 2^64)
+ * applied to an encrypted vector of wide slots by the diagonal method, out = reduce(sum_r W_r * rot_{k_r}(x)).
+ * No reference function.  The definition, bit for bit: with ct [B][d][2][L][n] (NTT domain), a key set of R
+ * elements and H [B*d][R][2][L][n] = exacto_bfv_rotate_hoisted of the B*d limbs taken as BFV ciphertexts,
+ *     out [B][d][2][L][n] = exacto_dbfv_plain_mul_sum(cts[b][r][j] = H[b*d + j][r], K = R, polys = 2,
+ *                                                     pts [R][d][n] with pt_batch = 1),
+ * canonical residues: the same SmallReps::compute_simple fold and the same skipped pairs, the same depth rule
+ * (an input depth >= 1 is NotImplemented, depth_out[b] = depth_ct[b] + 1; depth_ct host [B], NULL = 0;
+ * depth_out NULL allowed), and the same bits on both key-switch paths.  pts are plaintext coefficients (any
+ * u64); in the slot case what exacto_dbfv_batch_encode writes for R value vectors.
+ *
+ * exacto_dbfv_rotate_hoisted: ct [B][d][2][L][n] -> out [B][R][d][2][L][n]: every out[b][r] is a dBFV
+ *   ciphertext, limb j of it bit for bit exacto_bfv_rotate_hoisted's out[b*d + j][r]; written in place by the
+ *   rotation kernels, no copy.  out must not overlap ct; d == 0 is InvalidParam.  exacto_ctx_set_chunk counts
+ *   BFV limbs: a chunk is max(1, chunk / d) dBFV ciphertexts.
+ * exacto_dbfv_diagonals_create: pts [R][d][n] (host memory, _dev: device memory) lifted once (reduced mod each
+ *   q_l and transformed, as the products lift them) into a device buffer [R][d][L][n] owned by the handle; pts
+ *   may be released when the call returns.  InvalidParam: a null pointer, d == 0 or d > 64, R == 0 or above
+ *   65535.  The caller owns the handle and destroys it BEFORE destroying the context it was created on.
+ * exacto_dbfv_diagonals_destroy: NULL is a no-op.
+ * exacto_dbfv_diagonals_info: R, d, and the route a transform of d digits takes on the context the handle was
+ *   made on (0: the staged route, rotations into per-chunk scratch read in place by the plaintext-product
+ *   kernel: the default; 1: the fused kernel, dbfv_hoist.hip, after exacto_ctx_set_dbfv_lt_fused(ctx, 1) on the
+ *   limb-wise key switch with d <= 8), as it was when the handle was made; any out pointer may be NULL.
+ * exacto_ctx_set_dbfv_lt_fused: on != 0 sends the limb-wise key switch with d <= 8 through the fused kernel, on
+ *   = 0 (the default: the staged route measured twice as fast) restores the staged route.  For tests and
+ *   measurements, not a tuning knob: no result depends on it.
+ * exacto_dbfv_linear_transform: the raw diagonals pts [R][d][n], lifted on every call into the context-owned
+ *   buffer exacto_ctx_set_plain_terms rotations at a time, a later group of rotations adding into out.
+ * exacto_dbfv_linear_transform_prepared: the handle instead of pts: no lift and no term chunking.
+ * Neither exacto_ctx_set_chunk nor exacto_ctx_set_plain_terms changes a result.  The scratch of the staged
+ * route stays within R outputs per chunk limb; on the fused route no rotated limb is ever stored.
+ * Errors of the two transforms, all before any launch and in this order: the context's; InvalidParam for a
+ * null pointer; a key set prepared on a context with other parameters, or for another key-switch path; those
+ * of DbfvParams::new; more than 64 digits; a handle from a context with another n, L or primes, then a handle
+ * whose R or d differs from the key set's R or from d; the depth error; a _dev buffer that is not 16-byte
+ * aligned; out overlapping ct or pts.  batch == 0 returns 0.  The _dev forms are asynchronous on the context's
+ * stream.  The state of exacto_bfv_apply_automorphism and of the BFV hoisted calls stays untouched. */
+typedef struct exacto_dbfv_diagonals exacto_dbfv_diagonals;
+int exacto_dbfv_rotate_hoisted(exacto_ctx* ctx, const exacto_galois_keyset* ks, size_t d, const uint64_t* ct,
+                               uint64_t* out, size_t batch);
+int exacto_dbfv_rotate_hoisted_dev(exacto_ctx* ctx, const exacto_galois_keyset* ks, size_t d, const uint64_t* ct,
+                                   uint64_t* out, size_t batch);
+int exacto_dbfv_diagonals_create(exacto_ctx* ctx, size_t d, size_t num_elements, const uint64_t* pts,
+                                 exacto_dbfv_diagonals** out);
+int exacto_dbfv_diagonals_create_dev(exacto_ctx* ctx, size_t d, size_t num_elements, const uint64_t* pts,
+                                     exacto_dbfv_diagonals** out);
+void exacto_dbfv_diagonals_destroy(exacto_dbfv_diagonals* dg);
+int exacto_dbfv_diagonals_info(const exacto_dbfv_diagonals* dg, size_t* num_elements, size_t* d, int* fused);
+int exacto_ctx_set_dbfv_lt_fused(exacto_ctx* ctx, int on);
+int exacto_dbfv_linear_transform(exacto_ctx* ctx, const exacto_galois_keyset* ks, size_t d, uint64_t base,
+                                 uint64_t dbfv_plain_modulus, const uint64_t* ct, const uint64_t* pts, uint64_t* out,
+                                 size_t batch, const uint32_t* depth_ct, uint32_t* depth_out);
+int exacto_dbfv_linear_transform_dev(exacto_ctx* ctx, const exacto_galois_keyset* ks, size_t d, uint64_t base,
+                                     uint64_t dbfv_plain_modulus, const uint64_t* ct, const uint64_t* pts,
+                                     uint64_t* out, size_t batch, const uint32_t* depth_ct, uint32_t* depth_out);
+int exacto_dbfv_linear_transform_prepared(exacto_ctx* ctx, const exacto_galois_keyset* ks, size_t d, uint64_t base,
+                                          uint64_t dbfv_plain_modulus, const uint64_t* ct,
+                                          const exacto_dbfv_diagonals* dg, uint64_t* out, size_t batch,
+                                          const uint32_t* depth_ct, uint32_t* depth_out);
+int exacto_dbfv_linear_transform_prepared_dev(exacto_ctx* ctx, const exacto_galois_keyset* ks, size_t d,
+                                              uint64_t base, uint64_t dbfv_plain_modulus, const uint64_t* ct,
+                                              const exacto_dbfv_diagonals* dg, uint64_t* out, size_t batch,
+                                              const uint32_t* depth_ct, uint32_t* depth_out);
+
 /* Plaintext-ciphertext operations (CoeffsToSlots' linear layer), all in the NTT domain.
  * ct/out [B][polys][L][n]; pt [B][n] plaintext coefficients (any u64, reduced mod each q_i).
  *   bfv_plain_mul     replaces bfv::eval::bfv_plain_mul      (src/bfv/eval.rs:468-486)
